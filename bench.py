@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: VJF online filtering step throughput (trial-timesteps/sec) + ELBO.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "config B"): 4096 trials per GPU, d_z=10, d_y=50, 200 RBF centres,
 recognition hidden=[128], Gaussian likelihood, fp32, synthetic "RBF data", explicit pre-drawn noise, sgd=True / update=True /
 warm_up=False.  One "step" = one VJF.filter call on the whole batch (everything of the step, incl. the serial RLS update).
-W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize -> `value`.  After that region the
-sequence continues for --repeats - 1 further regions of K steps (reported as `ms_per_step_repeats` with their median: the
-spread of the measurement; they do not enter `value`).  The ELBO of the first timed steps is compared with the
-fp64 oracle run from the model's own state on the same inputs (after the timed region).  With N > 1 GPUs the trials are
-sharded (4096 per GPU, weak scaling); the sums over trials go through RCCL inside the step.
+W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize -> `value`, `ms_per_step`.  With N > 1
+GPUs the trials are sharded (4096 per GPU, weak scaling); the sums over trials go through RCCL inside the step.
+
+A plain run does only that.  `--full` adds what stands beside the headline figure: the sequence continues for --repeats - 1
+further regions of K steps (reported as `ms_per_step_repeats` with their median: the spread of the measurement, SURVEY.md 8d;
+they do not enter `value`), the ELBO of the first timed steps is compared with the fp64 oracle run from the model's own state
+on the same inputs (after the timed regions), the CPU baseline and the fixed cost of a call are measured.
+`--dump-outputs DIR` writes what the last timed step returned (DIR/posterior_mean.npy, posterior_logvar.npy: (trials, d_z);
+loss.npy: loss, recon, dyn, entropy; float32).  The inputs are seeded: the same arguments give the same inputs on every run.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own ranks: a fresh child
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py <the same arguments>`), decided before anything of this
@@ -223,15 +227,21 @@ def cpu_baseline(c, config, s32, q0, y_cpu, eps_cpu, budget_s=12.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="regions of --steps steps each (the sequence continues): the first is `value`, "
-                                                           "all are listed with their median")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-elbo-check", action="store_true")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; configs A / D1 / E: 2000 / 100 / 40)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 20; configs D1 / E: 10 / 5)")
+    ap.add_argument("--repeats", type=int, default=None, help="regions of --steps steps each (the sequence continues): the first is `value`, "
+                                                              "all are listed with their median (default 1; with --full 5, configs D1 / E: 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beside the headline figure: further timed regions (--repeats), the ELBO of the "
+                         "timed steps against the fp64 oracle, the CPU baseline and the fixed cost of a call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (posterior mean and log-variance of every trial, the four loss terms) "
+                         "as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-elbo-check", action="store_true", help="--full without the ELBO check")
     ap.add_argument("--elbo-steps", type=int, default=10)
     ap.add_argument("--no-overlap", action="store_true", help="A/B: the per-step kernels in the one-stream order")
-    ap.add_argument("--no-call-cost", action="store_true", help="skip the fixed-cost-of-a-call measurement behind the timed regions (profiler runs)")
+    ap.add_argument("--no-call-cost", action="store_true", help="--full without the fixed-cost-of-a-call measurement behind the timed regions")
     ap.add_argument("--streams-route", action="store_true", help="A/B: the per-step three-stream route instead of the one-launch route")
     ap.add_argument("--config", default="B", choices=sorted(CFGS),
                     help="B: the headline workload (BASELINE configs[1]); A / C / E: configs[0] / [2] / [4]; D1: configs[3]'s 32768 trials "
@@ -249,6 +259,13 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1 only: run the sharded route (RCCL communicators inside the context) with a one-rank group")
     a = ap.parse_args()
+    for name in ("steps", "warmup", "repeats"):
+        v = getattr(a, name)
+        if v is not None and v < (0 if name == "warmup" else 1):
+            ap.error(f"--{name} {v}: out of range")
+    # what a plain run does not do: the checks and the other measurements are --full's
+    if not a.full:
+        a.no_cpu_baseline = a.no_elbo_check = a.no_call_cost = True
 
     # stdout carries the ONE JSON line and nothing else: libraries that write to file descriptor 1 (RCCL prints a version banner
     # there when a communicator is made) go to stderr for the length of the run
@@ -285,18 +302,19 @@ def main():
 
     import vjf_amd
     c = dict(CFGS[a.config])
-    K, W, R = a.steps, a.warmup, max(1, a.repeats)
-    if a.config == "E" and a.steps == 200:
-        K, W, R = 40, 5, 3                                      # ms-scale steps: keep the default run short
+    # defaults per configuration; an explicit --steps / --warmup / --repeats is taken as given
+    K, W, R = {"E": (40, 5, 3),                                 # ms-scale steps: keep the default run short
+               "D1": (100, 10, 3),
+               "A": (2000, 20, 5)}.get(a.config, (200, 20, 5))  # A: SURVEY.md 8d, T_meas = 2000 for the single-trial configuration
+    K = K if a.steps is None else a.steps
+    W = W if a.warmup is None else a.warmup
+    R = (R if a.full else 1) if a.repeats is None else a.repeats
+    if a.config == "E":
         a.elbo_steps = min(a.elbo_steps, 2)                     # (an fp64 oracle step takes seconds at this size)
     if a.config == "D1":
         a.elbo_steps = min(a.elbo_steps, 3)
-        if a.steps == 200:
-            K, W, R = 100, 10, 3
     if world > 1:
         a.elbo_steps = min(a.elbo_steps, 2)                     # (the fp64 oracle on the batch of ALL ranks)
-    if a.config == "A" and a.steps == 200:
-        K = 2000                                                # T_meas = 2000 for the single-trial configuration
     T = W + K * R
     fkw = {"train": dict(sgd=True, update=True, warm_up=False), "warmup": dict(sgd=True, update=True, warm_up=True),
            "infer": dict(sgd=False, update=False, warm_up=False), "sgd-only": dict(sgd=True, update=False, warm_up=False)}[a.flags]
@@ -337,7 +355,7 @@ def main():
                 m.set_collectives(1)
             return m
         model = make_model()
-        Td = max(T, 100) if a.config == "B" else T                  # (the call-cost measurement behind the timed regions takes 100 steps)
+        Td = max(T, 100) if a.config == "B" and a.full else T       # (the call-cost measurement and the CPU baseline behind the timed regions take up to 100 steps)
         y = synth_data(c, Td, 1234 + rank, dev, a.config)           # each rank filters its own trials
         eps = torch.randn(Td, 2, c["B"], c["dz"], device=dev, generator=torch.Generator(device=dev).manual_seed(4321 + rank))
         cdev = dev if ctrl == "nccl" else "cpu"                      # where the control plane's tensors live
@@ -464,7 +482,7 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             walls.append(float(tt.item())); devs.append(ev0.elapsed_time(ev1) * 1e-3); enqs.append(enq)
             elbos.append(float(-loss[:, 0].mean().item()))
-            if r == 0:
+            if r == 0 and not a.no_elbo_check:
                 first_losses = loss[:min(a.elbo_steps, K)].cpu().numpy().astype(np.float64)
             q = vjf_amd.Gaussian(mu[-1], lv[-1])
         if watchdog is not None:
@@ -474,8 +492,17 @@ def main():
         rccl_ranks = model.comm_ranks() if world > 1 or a.force_dist else None
         if world > 1 and not getattr(model, "_comm_ok", False):
             route = f"caller-side all-reduce (vjf_filter_local / torch.distributed[{ctrl}] / vjf_filter_global per step)"
+        if a.dump_outputs:                                           # what the last timed step returned (N > 1: the trials of all ranks)
+            dump = {"posterior_mean": gather_batch(mu[-1], 0), "posterior_logvar": gather_batch(lv[-1], 0),
+                    "loss": loss[-1]}                                # (loss, recon, dyn, entropy)
+            if rank == 0:
+                dump = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in dump.items()}
+                assert sum(v.nbytes for v in dump.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+                os.makedirs(a.dump_outputs, exist_ok=True)
+                for k, v in dump.items():
+                    np.save(os.path.join(a.dump_outputs, k + ".npy"), v)
         wall_max, dev_s, enq = walls[0], devs[0], enqs[0]           # `value`: the first region = exactly K steps after W warm-up steps
-        ne = first_losses.shape[0]
+        ne = 0 if first_losses is None else first_losses.shape[0]
         # what the checker needs of the other ranks: their trials' inputs of the first `ne` timed steps and the posterior they started from
         y_chk = eps_chk = q0 = None
         if want_check and not a.no_elbo_check:

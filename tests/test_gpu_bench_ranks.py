@@ -28,7 +28,7 @@ def _run(args, extra_env=None, timeout=600):
 
 
 def test_bench_starts_its_own_two_ranks_on_one_gpu():
-    j = _run(["--gpus", "2", "--steps", "6", "--warmup", "3", "--repeats", "2", "--no-cpu-baseline"],
+    j = _run(["--gpus", "2", "--steps", "6", "--warmup", "3", "--repeats", "2", "--no-cpu-baseline", "--full"],
              {"VJF_BENCH_BACKEND": "gloo"})
     assert j["metric"] == "trial-timesteps/sec" and j["unit"] == "trial-timesteps/s"
     assert j["n_gpus"] == 2 and j["steps"] == 6 and j["warmup"] == 3 and j["scaling"] == "weak"
@@ -45,7 +45,7 @@ def test_bench_starts_its_own_two_ranks_on_one_gpu():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    j = _run(["--steps", "10", "--warmup", "3", "--repeats", "1", "--no-call-cost"])
+    j = _run(["--steps", "10", "--warmup", "3", "--repeats", "1", "--no-call-cost", "--full"])
     assert j["n_gpus"] == 1 and j["route"] == "one-launch" and j["dist"] is None
     assert j["roofline"]["bound"] == "mfma" and 0 < j["roofline"]["frac"] < 1
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["value"] > 0
@@ -56,7 +56,7 @@ def test_bench_falls_back_when_the_in_library_route_fails_in_its_warm_up():
     """The in-library RCCL route has never run with two real ranks on the builder's boxes; if a wait of its warm-up steps gives up
     (or the library returns an error) on ANY rank, every rank starts over with a fresh model on the caller-side sums and the line
     says so.  Injected here (rank 0 reports a failed warm-up once): the run still ends with a valid line whose ELBO matches."""
-    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"],
+    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"],
              {"VJF_BENCH_BACKEND": "gloo", "VJF_BENCH_FAKE_NATIVE_FAILURE": "1"})
     d = j["dist"]
     assert d["sums_over_ranks"].startswith("caller (") and "injected" in d["native_route_error"]
@@ -68,7 +68,7 @@ def test_bench_measures_the_caller_side_route_first_and_keeps_its_line():
     follows under a watchdog.  Here (two ranks on ONE GPU, where RCCL cannot make its communicators) the in-library attempt fails
     one way or another -- an error of the communicator's creation, or no answer until the watchdog -- and the run still ends with
     exit code 0 and a valid line of the caller-side route that says what happened."""
-    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"],
+    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"],
              {"VJF_BENCH_BACKEND": "gloo", "VJF_BENCH_TEST_SAFE": "1", "VJF_BENCH_WARMUP_TIMEOUT": "40"})
     d = j["dist"]
     assert d["native_route_error"], d
@@ -78,7 +78,7 @@ def test_bench_measures_the_caller_side_route_first_and_keeps_its_line():
 
 
 def test_bench_ends_with_the_kept_line_when_the_in_library_route_never_comes_back():
-    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"],
+    j = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full"],
              {"VJF_BENCH_BACKEND": "gloo", "VJF_BENCH_TEST_SAFE": "1", "VJF_BENCH_FAKE_NATIVE_HANG": "1", "VJF_BENCH_WARMUP_TIMEOUT": "25"})
     d = j["dist"]
     assert "did not finish in time" in d["native_route_error"], d

@@ -255,7 +255,7 @@ def test_replay_with_several_tiles_per_workgroup(vjf):
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ["B", "E"])
 def test_bench_line_contract(config):
-    """`bench.py` as the round driver runs it (fewer steps): ONE JSON line with the contract's fields, the roofline and cpu_baseline
+    """`bench.py --full` (fewer steps): ONE JSON line with the contract's fields, the roofline and cpu_baseline
     objects, the ELBO of the timed steps checked against the oracle inside the run, status clean.  `--config E`: the extra line of
     configs[4] (its ELBO check is the oracle at B = 4096 on the GEMM-per-layer trial path)."""
     import json
@@ -264,7 +264,7 @@ def test_bench_line_contract(config):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     extra = [] if config == "B" else ["--config", "E", "--elbo-steps", "2"]
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--repeats", "2"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--repeats", "2", "--full"] + extra,
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -285,6 +285,38 @@ def test_bench_line_contract(config):
     if config == "B":                                          # the fixed cost of a call, measured behind the timed regions
         cc = d["call_cost"]
         assert 0.0 < cc["fixed_us_per_call"] < 400.0 and 0.0 < cc["single_filter_call_us"] < 600.0 and 20.0 < cc["steady_us_per_step"] < 200.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run: exactly --steps timed steps in one region, the headline fields, none of --full's measurements.
+    `--dump-outputs` writes what the last timed step returned; a second run with the same arguments dumps the same arrays, bit for
+    bit (seeded inputs, a deterministic step)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i in range(2):
+        d_out = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["metric"] == "trial-timesteps/sec" and d["unit"] == "trial-timesteps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["repeats"] == 1 and len(d["ms_per_step_repeats"]) == 1
+        assert abs(d["value"] - 4096 * 7 / (d["ms_per_step"] * 1e-3 * 7)) / d["value"] < 1e-6
+        assert "cpu_baseline" not in d and d["elbo_check"] is None and d["call_cost"] is None and d["status_bits"] == 0
+        arrs = {k: np.load(d_out / f"{k}.npy") for k in ("posterior_mean", "posterior_logvar", "loss")}
+        assert arrs["posterior_mean"].shape == arrs["posterior_logvar"].shape == (4096, 10) and arrs["loss"].shape == (4,)
+        for v in arrs.values():
+            assert v.dtype == np.float32 and np.isfinite(v).all()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_resident_column_loop_barrier_timeout_raises(vjf, monkeypatch):

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=${1:-r04}
 O=gpurun_out
 mkdir -p $O
-run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err || { echo "bench $name failed"; tail -5 $O/${TAG}_bench_$name.err; exit 1; }; }
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > $O/${TAG}_bench_$name.json 2> $O/${TAG}_bench_$name.err || { echo "bench $name failed"; tail -5 $O/${TAG}_bench_$name.err; exit 1; }; }
 run driver_settings --steps 20 --warmup 5
 run configA --config A
 run configC --config C

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile of the benchmarked command (run on the GPU box from the repo root):  tools/profile_round.sh r03
-#   1. bench.py (default flags)                                        -> gpurun_out/<tag>_bench.json
+#   1. bench.py --full                                                 -> $O/<tag>_bench.json
 #   2. rocprofv3 --kernel-trace --stats of the same workload           -> gpurun_out/<tag>_kernel_stats.csv (+ _meta.json)
 #   3. rocprofv3 --pmc, one counter set per pass, --kernel-trace only  -> gpurun_out/<tag>_pmc_traffic.json, <tag>_pmc_sq.json
 # HBM traffic as MI355X_MICROARCH.md prescribes: FETCH_SIZE and WRITE_SIZE in separate passes, KB units, FETCH_SIZE x2 on gfx950.
@@ -12,7 +12,7 @@ K=${2:-200}
 W=20
 O=gpurun_out
 mkdir -p $O
-timeout -k 10 400 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
 echo "bench: $(python -c "import json;d=json.load(open('$O/${TAG}_bench.json'));print(d['value'], d['ms_per_step'], d['ms_per_step_repeats'], d['elbo_check'])")"
 rm -rf $O/${TAG}_stats
 # (every profiled run must END cleanly: round 2's runs died in the HIP runtime's exit handler -- the cooperative queue's teardown behind
