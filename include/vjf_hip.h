@@ -118,6 +118,17 @@ typedef struct vjf_config {
     int32_t device;                  /* HIP device ordinal */
 } vjf_config;
 
+/* Activation of the recognition layers (vjf/recognition.py:17-24: `activation`, one class for every layer; default Tanh).
+ * Supported: the activations whose derivative follows from the layer's output (the routes keep no pre-activation). */
+#define VJF_ACT_TANH 0
+#define VJF_ACT_RELU 1
+#define VJF_ACT_LEAKY_RELU 2   /* p0 = negative_slope >= 0 */
+#define VJF_ACT_ELU 3          /* p0 = alpha > 0 */
+#define VJF_ACT_SOFTPLUS 4     /* p0 = beta > 0, p1 = threshold >= 20 */
+#define VJF_ACT_SIGMOID 5
+#define VJF_ACT_HARDTANH 6     /* p0 = min_val < p1 = max_val (ReLU6: 0, 6) */
+typedef struct vjf_activation { int32_t kind; float p0, p1; } vjf_activation;
+
 typedef struct vjf_ctx vjf_ctx;
 
 int vjf_abi_version(void);
@@ -138,6 +149,10 @@ int vjf_workspace_size(const vjf_config* cfg, int64_t* bytes);
 int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t workspace_bytes,
                    void* stream, vjf_ctx** out);
 int vjf_ctx_destroy(vjf_ctx* ctx);
+/* Activation of the recognition layers (vjf/recognition.py:17-24; a new context has VJF_ACT_TANH).  Valid on a context that has
+ * not yet run a vjf_filter_* call (else an error); re-runs the one-launch residency check for the kernels it selects (when they
+ * cannot be resident the context takes the per-step route, and vjf_route says so).  Invalid kinds or parameters: < 0. */
+int vjf_set_activation(vjf_ctx* ctx, const vjf_activation* act);
 int vjf_set_stream(vjf_ctx* ctx, void* stream);
 /* Synchronises the stream, returns and clears the sticky status bits. */
 int vjf_get_status(vjf_ctx* ctx, uint32_t* status);
@@ -262,6 +277,12 @@ int vjf_recognition_forward(const float* y, const float* u, const float* mu_s, c
                             const float* lv_W, const float* lv_b, float* mu_t, float* lv_t, int32_t B,
                             int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
                             const int32_t* hidden, void* stream);
+/* Recognition.forward with an activation (vjf_recognition_forward is the VJF_ACT_TANH case).  Invalid kinds or parameters: < 0. */
+int vjf_recognition_forward_act(const float* y, const float* u, const float* mu_s, const float* lv_s,
+                                const float* const* rec_W, const float* const* rec_b, const float* mean_W,
+                                const float* lv_W, const float* lv_b, float* mu_t, float* lv_t, int32_t B,
+                                int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
+                                const int32_t* hidden, const vjf_activation* act, void* stream);
 /* functional.gaussian_loss (vjf/functional.py:32-75): lv1/lv2 NULL for point arguments;
  * logvar: device scalar; out: device scalar. */
 int vjf_gaussian_loss(const float* m1, const float* lv1, const float* m2, const float* lv2,

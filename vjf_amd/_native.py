@@ -30,6 +30,14 @@ SC_N_LIK, SC_N_TR, SC_LR_LIK, SC_LR_DEC, SC_LR_TR, SC_LR_REC, SC_FREEZE_DEC, SC_
 N_SCALARS = 16
 
 
+# activations of the recognition layers (vjf_activation)
+ACT_TANH, ACT_RELU, ACT_LEAKY_RELU, ACT_ELU, ACT_SOFTPLUS, ACT_SIGMOID, ACT_HARDTANH = range(7)
+
+
+class VjfActivation(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("p0", C.c_float), ("p1", C.c_float)]
+
+
 class VjfError(RuntimeError):
     """A C-ABI call returned an error code."""
 
@@ -53,6 +61,7 @@ SIGNATURES = {
     "vjf_workspace_size": [C.POINTER(VjfConfig), C.POINTER(C.c_int64)],
     "vjf_ctx_create": [C.POINTER(VjfConfig), _P, _P, C.c_int64, _P, C.POINTER(_P)],
     "vjf_ctx_destroy": [_P],
+    "vjf_set_activation": [_P, C.POINTER(VjfActivation)],
     "vjf_set_stream": [_P, _P],
     "vjf_get_status": [_P, C.POINTER(_U)],
     "vjf_set_overlap": [_P, _I],
@@ -76,6 +85,8 @@ SIGNATURES = {
     "vjf_blr_kalman": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_recognition_forward": [_P, _P, _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
                                 C.POINTER(_I), _P],
+    "vjf_recognition_forward_act": [_P, _P, _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P, _P, _P, _P, _I, _I, _I, _I, _I,
+                                    C.POINTER(_I), C.POINTER(VjfActivation), _P],
     "vjf_gaussian_loss": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "vjf_gaussian_entropy": [_P, _P, _I, _I, _P],
     "vjf_poisson_loss": [_P, _P, _P, _I, _I, _P],

@@ -377,6 +377,9 @@ struct vjf_ctx {
     bool handoff_acquire;  // VJF_HANDOFF_ACQUIRE=1: the one-launch route's waits acquire at agent scope beside the sc1 loads (default: sc1 loads alone)
     bool force_streams;    // vjf_set_overlap(ctx, 3): the three-stream per-step route on a single rank too (A/B measurements)
     bool mega_ok;          // the plan fits the one-launch route (vjf_mega_kernel.h)
+    bool mega_plan;        // mega_plan_ok(plan): the route's tables exist (mega_ok also needs the residency check of the context's kernels)
+    VjfAct act;            // activation of the recognition layers (vjf_set_activation; VJF_ACT_TANH: the Tanh kernels)
+    bool ran;              // a vjf_filter_* call has run on the context (vjf_set_activation is refused from then on)
     int ncu;               // compute units of the device: the one-launch grid has one workgroup per CU
     int mega_wg_per_cu;    // workgroups of vjf_mega_kernel a compute unit can hold (occupancy query): the residency check of the route
     int lite_wg_per_cu;    // the same for vjf_mega_lite_kernel (the launches without an RLS update)
@@ -436,6 +439,67 @@ int vjf_workspace_size(const vjf_config* cfg, int64_t* bytes) {
     return 0;
 }
 
+namespace {
+// The residency check of the one-launch route, made on the kernels the context will launch (vjf_mega_kernel / vjf_mega_lite_kernel,
+// or their act instantiations for another activation): workgroups per compute unit from the occupancy query; a context whose full
+// grid cannot be resident takes the per-step route.
+void mega_residency(vjf_ctx* c) {
+    c->mega_ok = c->mega_plan;
+    c->mega_wg_per_cu = 0; c->lite_wg_per_cu = 0;
+    if (!c->mega_ok) return;
+    auto per_cu = [](auto kernel) {
+        allow_lds(kernel, kMegaLds);
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, VJF_MG_THREADS, kMegaLds) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
+        return nb;
+    };
+    const bool act = c->act.kind != VJF_ACT_TANH;
+    c->mega_wg_per_cu = act ? per_cu(vjf_mega_act_kernel) : per_cu(vjf_mega_kernel);
+    if (c->mega_wg_per_cu < 1) c->mega_ok = false;
+    c->lite_wg_per_cu = act ? per_cu(vjf_mega_lite_act_kernel) : per_cu(vjf_mega_lite_kernel);
+}
+// Count the context in its device's live one-launch contexts (d->mu held) while it is on that route: from the second one on, their
+// resident grids are chained (whichever kernels they run).
+void count_mega(vjf_ctx* c, DevShared* d) {
+    if (c->mega_counted && !c->mega_ok) {
+        c->mega_counted = false;
+        if (d->mega_ctxs > 0) --d->mega_ctxs;
+    }
+    if (c->mega_ok && !c->mega_counted) {
+        c->mega_counted = true;
+        if (++d->mega_ctxs == 2 && !d->chained) {
+            (void)hipDeviceSynchronize();                           // (the first context's launches so far carry no event)
+            if (!d->last) (void)hipEventCreateWithFlags(&d->last, hipEventDisableTiming);
+            d->chained = d->last != nullptr;
+        }
+    }
+}
+// A valid vjf_activation -> *out (0), else < 0 with vjf_last_error set (include/vjf_hip.h: the supported set and its parameters)
+int act_check(const vjf_activation* a, const char* who, VjfAct* out) {
+    if (!a) return fail(-1, "%s: null activation", who);
+    const float p0 = a->p0, p1 = a->p1;
+    switch (a->kind) {
+        case VJF_ACT_TANH: case VJF_ACT_RELU: case VJF_ACT_SIGMOID: break;
+        case VJF_ACT_LEAKY_RELU:
+            if (!(p0 >= 0.f && std::isfinite(p0))) return fail(-31, "%s: LeakyReLU negative_slope=%g (needs a finite slope >= 0)", who, p0);
+            break;
+        case VJF_ACT_ELU:
+            if (!(p0 > 0.f && std::isfinite(p0))) return fail(-31, "%s: ELU alpha=%g (needs a finite alpha > 0)", who, p0);
+            break;
+        case VJF_ACT_SOFTPLUS:
+            if (!(p0 > 0.f && std::isfinite(p0))) return fail(-31, "%s: Softplus beta=%g (needs a finite beta > 0)", who, p0);
+            if (!(p1 >= 20.f)) return fail(-31, "%s: Softplus threshold=%g (needs >= 20)", who, p1);
+            break;
+        case VJF_ACT_HARDTANH:
+            if (!(std::isfinite(p0) && std::isfinite(p1) && p0 < p1)) return fail(-31, "%s: Hardtanh min_val=%g max_val=%g (needs finite min_val < max_val)", who, p0, p1);
+            break;
+        default: return fail(-30, "%s: activation kind %d (supported: VJF_ACT_TANH .. VJF_ACT_HARDTANH)", who, (int)a->kind);
+    }
+    *out = VjfAct{a->kind, p0, p1};
+    return 0;
+}
+}  // namespace
+
 int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t workspace_bytes, void* stream,
                    vjf_ctx** out) {
     if (!cfg || !state || !workspace || !out) return fail(-1, "vjf_ctx_create: null argument");
@@ -480,6 +544,8 @@ int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t
     // timing test (tests/test_gpu_handoffs.py) runs in both.
     { const char* ha = getenv("VJF_HANDOFF_ACQUIRE"); c->handoff_acquire = ha && atoi(ha) != 0; }
     c->mega_ok = mega_plan_ok(P);
+    c->mega_plan = c->mega_ok;
+    c->act = VjfAct{VJF_ACT_TANH, 0.f, 0.f}; c->ran = false;
     {
         int v = 0;
         VJF_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, cfg->device));
@@ -567,17 +633,7 @@ int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t
     allow_lds(vjf_chol_lds_kernel<32>, c->lds_chol);
     allow_lds(vjf_rls_pair_kernel<4>, c->lds_chol); allow_lds(vjf_rls_pair_kernel<8>, c->lds_chol);
     allow_lds(vjf_rls_pair_kernel<12>, c->lds_chol); allow_lds(vjf_rls_pair_kernel<16>, c->lds_chol);
-    if (c->mega_ok) {
-        allow_lds(vjf_mega_kernel, kMegaLds);
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, vjf_mega_kernel, VJF_MG_THREADS, kMegaLds) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
-        c->mega_wg_per_cu = nb;
-        if (nb < 1) c->mega_ok = false;
-        allow_lds(vjf_mega_lite_kernel, kMegaLds);
-        nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, vjf_mega_lite_kernel, VJF_MG_THREADS, kMegaLds) != hipSuccess) { (void)hipGetLastError(); nb = 0; }
-        c->lite_wg_per_cu = nb;
-    }
+    mega_residency(c);
     if (DevShared* d = dev_shared(cfg->device)) {
         std::lock_guard<std::mutex> lk(d->mu);
         if (!d->mirror_h) {
@@ -589,12 +645,7 @@ int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t
             }
             (void)hipGetLastError();                                // (without the page: no early notice, the status word still tells)
         }
-        if (c->mega_ok) c->mega_counted = true;
-        if (c->mega_ok && ++d->mega_ctxs == 2 && !d->chained) {
-            (void)hipDeviceSynchronize();                           // (the first context's launches so far carry no event)
-            if (!d->last) (void)hipEventCreateWithFlags(&d->last, hipEventDisableTiming);
-            d->chained = d->last != nullptr;
-        }
+        count_mega(c, d);
     }
     *out = c;
     return 0;
@@ -820,6 +871,23 @@ void launch_wide_gemm(const VjfWideGemm& g0, hipStream_t st) {
         hipLaunchKernelGGL(vjf_wide_gemm_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64), dim3(256), 0, st, g);
 }
 
+// the matrix-core trial kernel of the context's activation
+void launch_trial_mfma(const vjf_ctx* c, int nblk, hipStream_t st, const VjfTrialMfmaArgs& m) {
+    if (c->act.kind == VJF_ACT_TANH)
+        hipLaunchKernelGGL(vjf_trial_mfma_kernel, dim3(nblk), dim3(VJF_K1M_THREADS), c->lds_k1m, st, c->plan, m);
+    else
+        hipLaunchKernelGGL(vjf_trial_mfma_act_kernel, dim3(nblk), dim3(VJF_K1M_THREADS), c->lds_k1m, st, c->plan, m, c->act);
+}
+
+// the element-wise activation pass of the wide route (vjf_wide_act_kernel): X <- act(X), or X <- X act'(H) with H non-null
+void launch_wide_act(const vjf_ctx* c, float* X, int ldx, const float* H, int ldh, int M, int N, const int* ok, hipStream_t st) {
+    VjfWideAct w{};
+    w.X = X; w.ldx = ldx; w.H = H; w.ldh = ldh; w.M = M; w.N = N; w.mode = H ? WACT_DH : WACT_FWD; w.act = c->act; w.ok = ok;
+    const size_t total = (size_t)M * N;
+    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(vjf_wide_act_kernel, dim3(grid), dim3(256), 0, st, w);
+}
+
 // K1 of the per-step routes.  part: 0 whole step, 1 forward half, 2 backward half (matrix-core kernel only)
 int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bool count_fwd = false,
                  const unsigned* rls_done = nullptr, unsigned rls_target = 0) {
@@ -832,7 +900,7 @@ int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bo
         if (a.replay) {                                            // the backward half again; counted only where an RLS update on another
             m.part = 2;                                            // stream must not overwrite W, w_chol, sigma under it (count_fwd)
             if (count_fwd) m.done = (unsigned*)(c->ws + c->cv.flags) + 16;
-            hipLaunchKernelGGL(vjf_trial_mfma_kernel, dim3(nblk), dim3(VJF_K1M_THREADS), c->lds_k1m, st, P, m);
+            launch_trial_mfma(c, nblk, st, m);
             VJF_HIP(hipGetLastError());
             return 0;
         }
@@ -840,7 +908,7 @@ int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bo
         if (part != 1) c->k1_count += (unsigned)nblk;
         if (part == 1 && count_fwd) { m.fwd_done = (unsigned*)(c->ws + c->cv.flags) + 48; c->fwd_count += (unsigned)nblk; }
         m.stamps = c->stamps ? (unsigned long long*)(c->ws + c->cv.work + vjf_serial_work_floats(P) * 4) : nullptr;
-        hipLaunchKernelGGL(vjf_trial_mfma_kernel, dim3(nblk), dim3(VJF_K1M_THREADS), c->lds_k1m, st, P, m);
+        launch_trial_mfma(c, nblk, st, m);
     } else {
         // working set beyond LDS: one GEMM over all trials per layer (vjf_trial_wide.h)
         VjfWideArgs w{};
@@ -849,6 +917,8 @@ int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bo
         const size_t Bz = (size_t)a.B;
         w.XU = wb; w.PM = w.XU + Bz * P.dxu; w.PY = w.PM + Bz * P.dz + ((Bz + 3) / 4) * 4; w.Z = w.PY + Bz * P.dy;
         const float* S = c->state;
+        const bool act = c->act.kind != VJF_ACT_TANH;             // (the layers' activation: a pass behind the plain epilogues)
+        const int* okw = a.replay ? (const int*)a.replay_mask : nullptr;
         auto gemm = [&](const float* A_, int lda, const float* Bm, int ldb, float* C_, int ldc, int N, int K, int nt, int epi,
                         const float* bias = nullptr, const float* src = nullptr, int lds = 0) {
             VjfWideGemm g{};
@@ -865,7 +935,8 @@ int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bo
         int kin = P.din;
         for (int l = 0; l < P.L; ++l) {                            // h_l = tanh(h_{l-1} W_l^T + b_l)   (recognition.py:31-36)
             gemm(a.ACT + P.colA_act[l], P.ldA, S + P.off[VJF_SLOT_REC_W0 + 2 * l], kin, a.ACT + P.colA_act[l + 1], P.ldA, P.h[l], kin, 1,
-                 WEPI_TANH_BIAS, S + P.off[VJF_SLOT_REC_B0 + 2 * l]);
+                 act ? WEPI_BIAS : WEPI_TANH_BIAS, S + P.off[VJF_SLOT_REC_B0 + 2 * l]);
+            if (act) launch_wide_act(c, a.ACT + P.colA_act[l + 1], P.ldA, nullptr, 0, a.B, P.h[l], nullptr, st);   // (other activations)
             kin = P.h[l];
         }
         if (P.off[VJF_SLOT_LV_W] == P.off[VJF_SLOT_MEAN_W] + P.dz * kin) {   // the heads' weights lie one behind the other: ONE product, N = 2 dz
@@ -891,16 +962,23 @@ int launch_trial(vjf_ctx* c, const VjfTrialArgs& a, int part, hipStream_t st, bo
         const int hL = P.h[P.L - 1];
         if (P.off[VJF_SLOT_LV_W] == P.off[VJF_SLOT_MEAN_W] + P.dz * hL && P.colD_dlv == P.colD_dmu + P.dz)
             // the two heads' weights lie one behind the other in the state, their seeds side by side in DEL: ONE product with K = 2 dz
-            gemm(a.DEL + P.colD_dmu, P.ldD, S + P.off[VJF_SLOT_MEAN_W], hL, a.DEL + P.colD_da[P.L - 1], P.ldD, hL, 2 * P.dz, 0, WEPI_DTANH, nullptr,
-                 a.ACT + P.colA_act[P.L], P.ldA);
+            gemm(a.DEL + P.colD_dmu, P.ldD, S + P.off[VJF_SLOT_MEAN_W], hL, a.DEL + P.colD_da[P.L - 1], P.ldD, hL, 2 * P.dz, 0,
+                 act ? WEPI_NONE : WEPI_DTANH, nullptr, a.ACT + P.colA_act[P.L], P.ldA);
         else {
         gemm(a.DEL + P.colD_dmu, P.ldD, S + P.off[VJF_SLOT_MEAN_W], hL, a.DEL + P.colD_da[P.L - 1], P.ldD, hL, P.dz, 0, WEPI_NONE);
+        if (act)                                                   // (dh += dlv Wl, in place: C is its own source)
+            gemm(a.DEL + P.colD_dlv, P.ldD, S + P.off[VJF_SLOT_LV_W], hL, a.DEL + P.colD_da[P.L - 1], P.ldD, hL, P.dz, 0, WEPI_ADD_SRC, nullptr,
+                 a.DEL + P.colD_da[P.L - 1], P.ldD);
+        else
         gemm(a.DEL + P.colD_dlv, P.ldD, S + P.off[VJF_SLOT_LV_W], hL, a.DEL + P.colD_da[P.L - 1], P.ldD, hL, P.dz, 0, WEPI_ADDC_DTANH, nullptr,
              a.ACT + P.colA_act[P.L], P.ldA);
         }
-        for (int l = P.L - 1; l >= 1; --l)
+        if (act) launch_wide_act(c, a.DEL + P.colD_da[P.L - 1], P.ldD, a.ACT + P.colA_act[P.L], P.ldA, a.B, hL, okw, st);
+        for (int l = P.L - 1; l >= 1; --l) {
             gemm(a.DEL + P.colD_da[l], P.ldD, S + P.off[VJF_SLOT_REC_W0 + 2 * l], P.h[l - 1], a.DEL + P.colD_da[l - 1], P.ldD, P.h[l - 1], P.h[l], 0,
-                 WEPI_DTANH, nullptr, a.ACT + P.colA_act[l], P.ldA);
+                 act ? WEPI_NONE : WEPI_DTANH, nullptr, a.ACT + P.colA_act[l], P.ldA);
+            if (act) launch_wide_act(c, a.DEL + P.colD_da[l - 1], P.ldD, a.ACT + P.colA_act[l], P.ldA, a.B, P.h[l - 1], okw, st);
+        }
     }
     VJF_HIP(hipGetLastError());
     return 0;
@@ -1178,7 +1256,11 @@ int filter_seq_mega(vjf_ctx* c, int32_t T, int32_t B, const float* y, const floa
         if (d->last_valid && d->last_stream != c->stream) VJF_HIP(hipStreamWaitEvent(c->stream, d->last, 0));
         done = d->last;
     }
-    if (full) VJF_LAUNCH(vjf_mega_kernel, dim3(grid), dim3(VJF_MG_THREADS), kMegaLds, c->stream, done, Pk, A, C, Q);
+    if (c->act.kind != VJF_ACT_TANH) {                                     // (another activation: the act instantiations of the same grids)
+        if (full) VJF_LAUNCH(vjf_mega_act_kernel, dim3(grid), dim3(VJF_MG_THREADS), kMegaLds, c->stream, done, Pk, A, C, Q, c->act);
+        else VJF_LAUNCH(vjf_mega_lite_act_kernel, dim3(grid), dim3(VJF_MG_THREADS), kMegaLds, c->stream, done, Pk, A, c->act);
+    }
+    else if (full) VJF_LAUNCH(vjf_mega_kernel, dim3(grid), dim3(VJF_MG_THREADS), kMegaLds, c->stream, done, Pk, A, C, Q);
     else VJF_LAUNCH(vjf_mega_lite_kernel, dim3(grid), dim3(VJF_MG_THREADS), kMegaLds, c->stream, done, Pk, A);
     const hipError_t le = hipGetLastError();
     if (done && le == hipSuccess) { d->last_stream = c->stream; d->last_valid = true; }
@@ -1326,6 +1408,7 @@ static void chaos_refresh(const vjf_ctx* c) {
 int vjf_filter_local(vjf_ctx* c, int32_t B, const float* y, const float* u, const float* mu_s, const float* lv_s,
                      const float* eps_s, const float* eps_t, float* mu_t, float* lv_t, uint32_t flags) {
     if (!c) return fail(-1, "vjf_filter_local: null context");
+    c->ran = true;
     DeviceGuard on_device(c->cfg.device);                   // (every launch below goes to the context's device, whatever is current)
     VJF_CHAOS_REFRESH(c);
     VJF_HIP(hipSetDevice(c->cfg.device));
@@ -1488,6 +1571,7 @@ int filter_seq_packed(vjf_ctx* c, int32_t T, int32_t B, const float* y, const fl
 
 int vjf_filter_global(vjf_ctx* c, int32_t B_total, float* loss4, uint32_t flags) {
     if (!c) return fail(-1, "vjf_filter_global: null context");
+    c->ran = true;
     DeviceGuard on_device(c->cfg.device);                   // (every launch below goes to the context's device, whatever is current)
     VJF_CHAOS_REFRESH(c);
     if (B_total < 1) return fail(-20, "vjf_filter_global: B_total=%d", B_total);
@@ -1617,6 +1701,7 @@ int seq_chunk() {
 int vjf_filter_step(vjf_ctx* c, int32_t B, const float* y, const float* u, const float* mu_s, const float* lv_s,
                     const float* eps_s, const float* eps_t, float* mu_t, float* lv_t, float* loss4, uint32_t flags) {
     if (!c) return fail(-1, "vjf_filter_step: null context");
+    c->ran = true;
     DeviceGuard on_device(c->cfg.device);                   // (every launch below goes to the context's device, whatever is current)
     VJF_CHAOS_REFRESH(c);
     if (int rp = refuse_if_poisoned(c, "vjf_filter_step")) return rp;
@@ -1641,6 +1726,25 @@ int vjf_filter_step(vjf_ctx* c, int32_t B, const float* y, const float* u, const
     return filter_global_impl(c, B, loss4, flags, c->world > 1 ? nullptr : &ta);
 }
 
+int vjf_set_activation(vjf_ctx* ctx, const vjf_activation* act) {
+    VjfAct f{};
+    if (int rc = act_check(act, "vjf_set_activation", &f)) return rc;   // (the arguments first: no device call before them)
+    if (!ctx) return fail(-1, "vjf_set_activation: null context");
+    if (ctx->ran) return fail(-32, "vjf_set_activation: the context has already run a vjf_filter_* call");
+    DeviceGuard on_device(ctx->cfg.device);
+    ctx->act = f;
+    if (ctx->mfma_trial) {
+        if (f.kind == VJF_ACT_TANH) allow_lds(vjf_trial_mfma_kernel, ctx->lds_k1m);
+        else allow_lds(vjf_trial_mfma_act_kernel, ctx->lds_k1m);
+    }
+    mega_residency(ctx);                                    // (the residency check again, on the kernels the context will now launch)
+    if (DevShared* d = dev_shared(ctx->cfg.device)) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        count_mega(ctx, d);
+    }
+    return 0;
+}
+
 int vjf_route(vjf_ctx* c, uint32_t flags) {
     if (!c) return fail(-1, "vjf_route: null context");
     if (mega_route(c, flags)) return 1;
@@ -1654,6 +1758,7 @@ int vjf_route(vjf_ctx* c, uint32_t flags) {
 int vjf_filter_seq(vjf_ctx* c, int32_t T, int32_t B, const float* y, const float* u, const float* eps, const float* mu0,
                    const float* lv0, float* mu, float* lv, float* loss, uint32_t flags) {
     if (!c) return fail(-1, "vjf_filter_seq: null context");
+    c->ran = true;
     DeviceGuard on_device(c->cfg.device);                   // (every launch below goes to the context's device, whatever is current)
     VJF_CHAOS_REFRESH(c);
     if (T < 1) return fail(-23, "vjf_filter_seq: T=%d", T);
@@ -1782,62 +1887,12 @@ struct VjfRecArgs {
 };
 // Recognition.forward for 16 trials per workgroup: activations feature-major in LDS (ping-pong), every layer as 16 x 16 output
 // tiles on v_mfma_f32_16x16x4_f32 with the weights read as torch stores them (mma_tile<true>).
-__global__ __launch_bounds__(VJF_K1_THREADS) void vjf_recognition_kernel(VjfRecArgs A, int hmax) {
-    constexpr int TB = 16, LD = VJF_LDT, NW = VJF_K1_THREADS / 64;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int din = A.dy + A.du + 2 * A.dz;
-    float* s_in = smem;                  // din x LD
-    float* s_a = s_in + din * LD;        // hmax x LD
-    float* s_b = s_a + hmax * LD;        // hmax x LD
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b0 = blockIdx.x * TB, nb = min(TB, A.B - b0);
-    for (int i = tid; i < TB * din; i += VJF_K1_THREADS) {
-        const int b = i / din, c = i - b * din;
-        float v = 0.f;
-        if (b < nb) {
-            const size_t g = (size_t)(b0 + b);
-            if (c < A.dy) v = A.y[g * A.dy + c];
-            else if (c < A.dy + A.du) v = A.u[g * A.du + c - A.dy];
-            else if (c < A.dy + A.du + A.dz) v = A.mu_s[g * A.dz + c - A.dy - A.du];
-            else v = A.lv_s[g * A.dz + c - A.dy - A.du - A.dz];
-        }
-        s_in[c * LD + b] = v;
-    }
-    __syncthreads();
-    const int col = lane & 15, r4 = 4 * (lane >> 4);     // accumulator: row = r4 + r (output unit), column = trial
-    const float* xin = s_in; int kin = din;
-    float* cur = s_a; float* nxt = s_b;
-    for (int l = 0; l < A.L; ++l) {
-        const int hl = A.h[l];
-        const float* bias = A.b[l];
-        for (int t = wave; t * 16 < hl; t += NW) {
-            vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            mma_tile<true>(acc, A.W[l], kin, hl, t * 16, xin, kin, lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = t * 16 + r4 + r;
-                if (f < hl) cur[f * LD + col] = tanhf(acc[r] + bias[f]);
-            }
-        }
-        __syncthreads();
-        xin = cur; kin = hl;
-        float* t = cur; cur = nxt; nxt = t;
-    }
-    const int nt = (A.dz + 15) / 16;                         // tiles per head; the wavefronts take mean tiles, then log-variance tiles
-    for (int t = wave; t < 2 * nt; t += NW) {
-        const bool lvh = t >= nt;
-        const int f0 = (lvh ? t - nt : t) * 16;
-        vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        mma_tile<true>(acc, lvh ? A.lv_W : A.mean_W, kin, A.dz, f0, xin, kin, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int f = f0 + r4 + r;
-            if (f < A.dz && col < nb) {
-                if (lvh) A.lv_t[(size_t)(b0 + col) * A.dz + f] = acc[r] + A.lv_b[f];
-                else A.mu_t[(size_t)(b0 + col) * A.dz + f] = acc[r];
-            }
-        }
-    }
-}
+#define VJF_RECOGNITION_ACT 0
+#include "vjf_recognition_kernel.h"     // vjf_recognition_kernel
+#undef VJF_RECOGNITION_ACT
+#define VJF_RECOGNITION_ACT 1
+#include "vjf_recognition_kernel.h"     // vjf_recognition_act_kernel
+#undef VJF_RECOGNITION_ACT
 
 // features + target rows of the stand-alone RLS:  E[b] = [Phi(x_b) | target_b | 0]
 __global__ void vjf_rls_rows_kernel(const float* x, const float* c, const float* logw, const float* target, float* E,
@@ -2031,26 +2086,52 @@ int vjf_blr_kalman(const float* x, const float* target, const float* v, float di
     return 0;
 }
 
-int vjf_recognition_forward(const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
-                            const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
-                            float* lv_t, int32_t B, int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
-                            const int32_t* hidden, void* stream) {
+namespace {
+// vjf_recognition_forward(_act): act null or Tanh -> the Tanh kernel
+int recognition_forward(const char* who, const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
+                        const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
+                        float* lv_t, int32_t B, int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
+                        const int32_t* hidden, const VjfAct* act, void* stream) {
     if (!y || !mu_s || !lv_s || !rec_W || !rec_b || !mean_W || !lv_W || !lv_b || !mu_t || !lv_t || !hidden)
-        return fail(-1, "vjf_recognition_forward: null tensor");
-    if (udim > 0 && !u) return fail(-21, "vjf_recognition_forward: u is required when udim > 0");
-    if (n_hidden < 1 || n_hidden > VJF_MAX_HIDDEN) return fail(-3, "vjf_recognition_forward: n_hidden=%d", n_hidden);
-    if (B < 1) return fail(-20, "vjf_recognition_forward: bad shape");
+        return fail(-1, "%s: null tensor", who);
+    if (udim > 0 && !u) return fail(-21, "%s: u is required when udim > 0", who);
+    if (n_hidden < 1 || n_hidden > VJF_MAX_HIDDEN) return fail(-3, "%s: n_hidden=%d", who, n_hidden);
+    if (B < 1) return fail(-20, "%s: bad shape", who);
     VjfRecArgs a{};
     a.y = y; a.u = u; a.mu_s = mu_s; a.lv_s = lv_s; a.mean_W = mean_W; a.lv_W = lv_W; a.lv_b = lv_b; a.mu_t = mu_t; a.lv_t = lv_t;
     a.B = B; a.dy = ydim; a.du = udim; a.dz = xdim; a.L = n_hidden;
     int hmax = 0;
     for (int l = 0; l < n_hidden; ++l) { a.W[l] = rec_W[l]; a.b[l] = rec_b[l]; a.h[l] = hidden[l]; if (hidden[l] > hmax) hmax = hidden[l]; }
     const size_t lds = (size_t)VJF_LDT * (ydim + udim + 2 * xdim + 2 * hmax) * 4;
-    if (lds > kMaxLds - 1024) return fail(-10, "vjf_recognition_forward: layer widths do not fit LDS");
-    allow_lds(vjf_recognition_kernel, lds);
-    hipLaunchKernelGGL(vjf_recognition_kernel, dim3((B + 15) / 16), dim3(VJF_K1_THREADS), lds, (hipStream_t)stream, a, hmax);
+    if (lds > kMaxLds - 1024) return fail(-10, "%s: layer widths do not fit LDS", who);
+    if (act && act->kind != VJF_ACT_TANH) {
+        allow_lds(vjf_recognition_act_kernel, lds);
+        hipLaunchKernelGGL(vjf_recognition_act_kernel, dim3((B + 15) / 16), dim3(VJF_K1_THREADS), lds, (hipStream_t)stream, a, hmax, *act);
+    } else {
+        allow_lds(vjf_recognition_kernel, lds);
+        hipLaunchKernelGGL(vjf_recognition_kernel, dim3((B + 15) / 16), dim3(VJF_K1_THREADS), lds, (hipStream_t)stream, a, hmax);
+    }
     VJF_HIP(hipGetLastError());
     return 0;
+}
+}  // namespace
+
+int vjf_recognition_forward(const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
+                            const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
+                            float* lv_t, int32_t B, int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
+                            const int32_t* hidden, void* stream) {
+    return recognition_forward("vjf_recognition_forward", y, u, mu_s, lv_s, rec_W, rec_b, mean_W, lv_W, lv_b, mu_t, lv_t, B, ydim, udim,
+                               xdim, n_hidden, hidden, nullptr, stream);
+}
+
+int vjf_recognition_forward_act(const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
+                                const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
+                                float* lv_t, int32_t B, int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
+                                const int32_t* hidden, const vjf_activation* act, void* stream) {
+    VjfAct f{};
+    if (int rc = act_check(act, "vjf_recognition_forward_act", &f)) return rc;
+    return recognition_forward("vjf_recognition_forward_act", y, u, mu_s, lv_s, rec_W, rec_b, mean_W, lv_W, lv_b, mu_t, lv_t, B, ydim,
+                               udim, xdim, n_hidden, hidden, &f, stream);
 }
 
 int vjf_gaussian_loss(const float* m1, const float* lv1, const float* m2, const float* lv2, const float* logvar, float* out,

@@ -28,6 +28,7 @@
 #include "vjf_plan.h"
 #include "vjf_post_kernel.h"
 #include "vjf_trial_mfma_kernel.h"   // vjf_f32x4
+#include "vjf_act.h"
 
 #define VJF_MG_THREADS 512
 #define VJF_MG_WAVES 8
@@ -255,26 +256,7 @@ __device__ __forceinline__ float4 mg_ld4(__amdgpu_buffer_rsrc_t r, int float_ind
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 
-// tanh for the recognition layers (recognition.py:31-42), branch-free: the library's tanhf is ~70 VALU instructions with both of its
-// branches taken in every wavefront, eight calls per lane and layer -- 1.2 us of a 32-trial tile's 4.5-us layer on a part whose SIMDs
-// run VALU and MFMA instructions one after the other.  |x| < 0.55: x + x^3 P(x^2), the odd series through
-// x^15; else 1 - 2 / (e^{2|x|} + 1) on the hardware exp2 and reciprocal (within 1 ulp each): <= ~2-3 ulp of the result, <= 1.1e-7
-// absolute (emulated against fp64 over [-12, 12]: 1.8 ulp with exact exp2 / division); saturates to +-1 beyond |x| ~ 9, NaN stays NaN.
-__device__ __forceinline__ float mg_tanh(float x) {
-    const float ax = fabsf(x);
-    const float t = __builtin_amdgcn_exp2f(ax * 2.885390081777927f);          // e^{2|x|}
-    const float big = 1.f - 2.f * __builtin_amdgcn_rcpf(t + 1.f);
-    const float z = x * x;
-    float p = -1.4558343870513183e-3f;                                         // -929569/638512875
-    p = fmaf(p, z, 3.5921280365724810e-3f);                                    // 21844/6081075
-    p = fmaf(p, z, -8.8632355299021966e-3f);                                   // -1382/155925
-    p = fmaf(p, z, 2.1869488536155203e-2f);                                    // 62/2835
-    p = fmaf(p, z, -5.3968253968253971e-2f);                                   // -17/315
-    p = fmaf(p, z, 1.3333333333333333e-1f);                                    // 2/15
-    p = fmaf(p, z, -3.3333333333333331e-1f);                                   // -1/3
-    const float small = fmaf(p * z, x, x);
-    return ax < 0.55f ? small : copysignf(big, x);
-}
+// (mg_tanh, the Tanh kernels' tanh: vjf_act.h)
 
 // acc_g(row = 4*(lane>>4)+r, col = lane&15) += sum_{kb <= k < ke} Ag[k*lda + m0 + row] * Xs[k*LD + 16 g + col]   (g = 0, 1)
 // Rows m0 + i >= M contribute 0 (their A operand is read from a clamped address and masked at use).  kb is a multiple of 4.  The A operands come straight from L2 (k-major matrices: row k contiguous over the output features), 16 k-steps per batch,
@@ -654,8 +636,11 @@ __device__ __forceinline__ void mg_sum_losses(const VjfMegaArgs& A, int t, float
 // RLS = true: the training step (sgd + update, no warm-up) beside the RLS, Gram and operand roles -- every mode switch below is a
 // compile-time constant and the code is what it was before the other flag sets existed.  RLS = false (vjf_mega_lite_kernel: trial
 // and SGD roles only): warm-up, update=False, sgd=False, read from the launch's flags.
-template <bool RLS>
-__device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaArgs& A, float* smem, const int wg) {
+//
+// ACT = true (vjf_mega_act_kernel, vjf_mega_lite_act_kernel): the recognition layers' activation is `act` (vjf_act.h), read from
+// the launch's arguments, in place of tanh; ACT = false is the Tanh code and ignores `act`.
+template <bool RLS, bool ACT = false>
+__device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaArgs& A, float* smem, const int wg, const VjfAct act = VjfAct{}) {
     constexpr int LD = VJF_MG_LD, NW = VJF_MG_WAVES, NT = VJF_MG_THREADS, TR = VJF_MG_TR;
     const int tid0 = threadIdx.x;
     const int dz = P.dz, dy = P.dy, du = P.du, n = P.n, din = P.din, dxu = P.dxu;
@@ -1070,8 +1055,13 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                             const int f = tt * 16 + 4 * (lane >> 4) + r;
                             if (f < hl) {
                                 const float bf = tl ? ((mg_lds_cf*)bias_l)[f] : ((mg_glb_cf*)bias_g)[f];
-                                out[f * LD + (lane & 15)] = mg_tanh(acc0[r] + bf);
-                                out[f * LD + 16 + (lane & 15)] = mg_tanh(acc1[r] + bf);
+                                if (ACT) {
+                                    out[f * LD + (lane & 15)] = vjf_act_fwd(act, acc0[r] + bf);
+                                    out[f * LD + 16 + (lane & 15)] = vjf_act_fwd(act, acc1[r] + bf);
+                                } else {
+                                    out[f * LD + (lane & 15)] = mg_tanh(acc0[r] + bf);
+                                    out[f * LD + 16 + (lane & 15)] = mg_tanh(acc1[r] + bf);
+                                }
                             }
                         }
                     }
@@ -1424,7 +1414,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 const float* Wm = S + P.off[VJF_SLOT_MEAN_W];                  // (dz, hL): k-major for dh = dmu Wm + dlv Wl
                 const float* Wl = S + P.off[VJF_SLOT_LV_W];
                 const float* hact = s_act + (P.hsum - hL) * LD;
-                // dh_{l-1} = da_l W_l (1 - h_{l-1}^2)  into `dst`   (l = L: the heads)
+                // dh_{l-1} = da_l W_l (1 - h_{l-1}^2)  into `dst`   (l = L: the heads; ACT: act'(h_{l-1}) in place of 1 - h^2)
                 auto delta = [&](int l, const float* src, float* dst) {
                     const int hp = P.h[l - 1];
                     int aoff = 0;
@@ -1453,8 +1443,13 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                             const int k = tt * 16 + 4 * (lane >> 4) + r, b = lane & 15;
                             if (k < hp) {
                                 const float h0 = hprev[k * LD + b], h1 = hprev[k * LD + 16 + b];
-                                dst[k * LD + b] = acc0[r] * (1.f - h0 * h0);
-                                dst[k * LD + 16 + b] = acc1[r] * (1.f - h1 * h1);
+                                if (ACT) {
+                                    dst[k * LD + b] = acc0[r] * vjf_act_dh(act, h0);
+                                    dst[k * LD + 16 + b] = acc1[r] * vjf_act_dh(act, h1);
+                                } else {
+                                    dst[k * LD + b] = acc0[r] * (1.f - h0 * h0);
+                                    dst[k * LD + 16 + b] = acc1[r] * (1.f - h1 * h1);
+                                }
                             }
                         }
                     }
@@ -2514,6 +2509,54 @@ __global__ __launch_bounds__(VJF_MG_THREADS) void vjf_mega_lite_kernel(VjfPlan P
     if (mg_grid_resident(A.cnt, stw, A.alive_extra)) {
         const int idx = b - A.n_trial;
         if (b < A.n_trial) vjf_mega_trial<false>(P, A, lds, b);
+        else if (!(A.flags & (VJF_FLAG_SGD | VJF_FLAG_UPDATE))) {
+            // nothing changes between the steps: no SGD role -- the first n_sgd of these workgroups build the parameter image, and all
+            // n_mom of them (n_mom >= n_sgd, or none) are the moments role; the loss sums are the trial role's own (its last arriver)
+            if (idx < A.n_sgd) mg_build_image(P, A, idx, A.n_sgd);
+            if (idx < A.n_mom) vjf_mega_moments(P, A, lds, idx);
+        }
+        else if (idx < A.n_mom) vjf_mega_moments(P, A, lds, idx);
+        else vjf_mega_sgd<false>(P, A, lds, idx - A.n_mom);
+    }
+    mg_tell_host(stw, A.host_word);
+}
+
+// The same two grids with the recognition layers' activation `act` (vjf_act.h; vjf_set_activation) in place of tanh: extra
+// instantiations of the same roles, the Tanh kernels above keep their code (their source is left as it was, so that their ISA is).
+__global__ __launch_bounds__(VJF_MG_THREADS) void vjf_mega_act_kernel(VjfPlan P, VjfMegaArgs A, VjfCholArgs C, VjfPostArgs Q, VjfAct act) {
+    static_assert(VJF_CHOL_THREADS == VJF_MG_THREADS && VJF_POST_THREADS == VJF_MG_THREADS, "one workgroup size for every role");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ int s_dead;
+    if (threadIdx.x == 0) s_dead = 0;
+    __syncthreads();
+    int b = (int)blockIdx.x;
+    // the NEXT launch's counters are zeroed here, by one workgroup of the operand role, before anything else (that block belongs to the
+    // launch before this one, which is complete; the kernel boundary makes the zeros visible to the next launch): no memset in
+    // front of a launch
+    if (b == A.n_rls + A.n_trial + A.n_gram)
+        for (int i = threadIdx.x; i < MG_C_WORDS; i += VJF_MG_THREADS) A.cnt_next[i] = 0u;
+    float* stw = A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS;
+    if (mg_grid_resident(A.cnt, stw, A.alive_extra)) {
+        if (b == 0) vjf_chol_loop<16>(P, C, lds, &s_dead);
+        else if (b == 1) vjf_rls_post_loop(P, Q, lds, &s_dead, 2, 0);
+        else if (b < A.n_rls) vjf_rls_post_loop(P, Q, lds, &s_dead, 1, b - 2);
+        else if ((b -= A.n_rls) < A.n_trial) vjf_mega_trial<true, true>(P, A, lds, b, act);
+        else if ((b -= A.n_trial) < A.n_gram) vjf_mega_gram(P, A, lds, b);
+        else if ((b -= A.n_gram) < A.n_prep) vjf_mega_prep(P, A, lds, b);
+        else vjf_mega_sgd<true>(P, A, lds, b - A.n_prep);
+    }
+    mg_tell_host(stw, A.host_word);
+}
+
+__global__ __launch_bounds__(VJF_MG_THREADS) void vjf_mega_lite_act_kernel(VjfPlan P, VjfMegaArgs A, VjfAct act) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int b = (int)blockIdx.x;
+    if (b == A.n_trial)                                 // (the next launch's counter block: see vjf_mega_kernel)
+        for (int i = threadIdx.x; i < MG_C_WORDS; i += VJF_MG_THREADS) A.cnt_next[i] = 0u;
+    float* stw = A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS;
+    if (mg_grid_resident(A.cnt, stw, A.alive_extra)) {
+        const int idx = b - A.n_trial;
+        if (b < A.n_trial) vjf_mega_trial<false, true>(P, A, lds, b, act);
         else if (!(A.flags & (VJF_FLAG_SGD | VJF_FLAG_UPDATE))) {
             // nothing changes between the steps: no SGD role -- the first n_sgd of these workgroups build the parameter image, and all
             // n_mom of them (n_mom >= n_sgd, or none) are the moments role; the loss sums are the trial role's own (its last arriver)

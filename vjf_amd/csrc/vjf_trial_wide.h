@@ -11,6 +11,7 @@
 #include "vjf_chol_kernel.h"   // vjf_f32x16, vrow
 #include "vjf_plan.h"
 #include "vjf_trial_kernel.h"  // VjfTrialArgs
+#include "vjf_act.h"
 
 enum { WEPI_NONE = 0, WEPI_BIAS = 1, WEPI_TANH_BIAS = 2, WEPI_ADD_SRC = 3, WEPI_DTANH = 4, WEPI_ADDC_DTANH = 5, WEPI_SEED = 6, WEPI_HEADS = 7 };
 
@@ -55,6 +56,29 @@ __device__ __forceinline__ void vjf_wide_epilogue(const VjfWideGemm& g, int m, i
         default: break;
     }
     *c = v;
+}
+
+// A non-Tanh activation on this route (vjf_set_activation): the layer products run with the plain epilogues (WEPI_BIAS, WEPI_NONE,
+// WEPI_ADD_SRC) and this element-wise pass applies the activation or its derivative behind them -- the GEMM kernels and their
+// epilogue codes stay exactly the Tanh route's.  One extra read and write of a (B, h) block per layer and direction, beside GEMMs
+// of K >= 2 dz over the same block.
+enum { WACT_FWD = 0, WACT_DH = 1 };
+struct VjfWideAct {
+    float* X; int ldx;             // (M, N): WACT_FWD  X <- act(X);  WACT_DH  X <- X act'(H)
+    const float* H; int ldh;       // (M, N) layer output h (WACT_DH)
+    int M, N, mode;
+    VjfAct act;
+    const int* ok;                 // as VjfWideGemm::ok (a replay's launches do nothing when ok[0] == 0)
+};
+__global__ __launch_bounds__(256) void vjf_wide_act_kernel(VjfWideAct w) {
+    if (w.ok && w.ok[0] == 0) return;
+    const size_t total = (size_t)w.M * w.N;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int m = (int)(e / w.N), n = (int)(e - (size_t)m * w.N);
+        float* x = w.X + (size_t)m * w.ldx + n;
+        if (w.mode == WACT_FWD) *x = vjf_act_fwd(w.act, *x);
+        else *x *= vjf_act_dh(w.act, w.H[(size_t)m * w.ldh + n]);
+    }
 }
 
 #define VJF_WG_KC 16

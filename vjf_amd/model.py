@@ -405,6 +405,9 @@ class VJF(Module):
                                  ctypes.byref(ctx)), "vjf_ctx_create")
         self._ctx, self._ctx_batch = ctx, B
         _LIVE.add(self)
+        act = getattr(self.recognition, "act_code", (N.ACT_TANH, 0.0, 0.0))
+        if act[0] != N.ACT_TANH:                               # (another activation than the reference's default: the act kernels)
+            N.check(L.vjf_set_activation(ctx, ctypes.byref(N.VjfActivation(*act))), "vjf_set_activation")
         if getattr(self, "_collectives", 2) != 2:
             N.check(L.vjf_set_collectives(ctx, int(self._collectives)), "vjf_set_collectives")
         if getattr(self, "_overlap", 1) != 1:
