@@ -36,7 +36,7 @@ SUPPORTED = [
     (nn.Hardtanh, (6, -1.0, 1.0)),
     (functools.partial(nn.Hardtanh, -2.0, 0.5), (6, -2.0, 0.5)),
     (nn.ReLU6, (6, 0.0, 6.0)),
-    (lambda: nn.ReLU(), (1, 0.0, 0.0)),
+    pytest.param(lambda: nn.ReLU(), (1, 0.0, 0.0), id="lambda-ReLU"),     # (a fixed id: the repr of a lambda holds its address)
 ]
 
 
