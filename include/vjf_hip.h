@@ -254,6 +254,18 @@ int vjf_blr_predict(const float* x, const float* centroid, const float* logwidth
 int vjf_blr_sample(const float* x, const float* centroid, const float* logwidth, const float* w_mean,
                    const float* w_chol, const float* noise, float* out, float* w_scratch, int32_t B,
                    int32_t n, int32_t d, int32_t dout, void* stream);
+/* RBFDS.forecast (vjf/model.py:342-361) with the sampling branch of LinearRegression.forward (vjf/module.py:70-73) for every
+ * step, as one call:  x[0] = x0;  x[t+1] = x[t] + Phi([x[t], u[t]]) (w_mean + w_chol @ w_noise[t])  (+ s_noise[t] exp(tr_logvar / 2)).
+ * x (T+1,B,dout) out; u (T,B,du) or NULL (du = d - dout); w_noise (T,n,dout); s_noise (T,B,dout) or NULL; tr_logvar: device
+ * scalar (read only when s_noise is given).  w_chol is read as a dense matrix.  Asynchronous on `stream`, no host synchronisation;
+ * reads the state tensors, writes none.  Steps run in chunks (two launches each) whose weight samples live in `scratch`:
+ * >= vjf_forecast_scratch_size(T,n,dout) bytes, at most 8 MiB (+ four rows of padding) whatever T is, or one step's n dout floats where that is
+ * more; a chunk is at most 4096 steps.  -1 null tensor, -20 bad shape, -21 u missing with d > dout, -11 n (d) beyond one
+ * workgroup's LDS. */
+int vjf_forecast_scratch_size(int32_t T, int32_t n, int32_t dout, int64_t* bytes);
+int vjf_forecast_seq(const float* x0, const float* u, const float* w_noise, const float* s_noise, const float* centroid,
+                     const float* logwidth, const float* w_mean, const float* w_chol, const float* tr_logvar, float* x,
+                     void* scratch, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

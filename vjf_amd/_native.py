@@ -79,6 +79,8 @@ SIGNATURES = {
     "vjf_rbf_forward": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vjf_blr_predict": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_blr_sample": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vjf_forecast_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
+    "vjf_forecast_seq": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vjf_rls_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_blr_rls": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_kalman_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],

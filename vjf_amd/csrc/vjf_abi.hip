@@ -463,6 +463,9 @@ __global__ __launch_bounds__(VJF_K1_THREADS) void vjf_blr_predict_kernel(VjfPred
     }
 }
 
+// the sampled roll-out of vjf_forecast_seq: vjf_fc_weights_kernel, vjf_fc_rollout_kernel
+#include "vjf_forecast_kernel.h"
+
 struct VjfRecArgs {
     const float* y; const float* u; const float* mu_s; const float* lv_s;
     const float* W[VJF_MAX_HIDDEN]; const float* b[VJF_MAX_HIDDEN];
@@ -599,6 +602,83 @@ int vjf_blr_sample(const float* x, const float* centroid, const float* logwidth,
     }
     VJF_HIP(hipGetLastError());
     return launch_predict("vjf_blr_sample", VjfPredArgs{x, centroid, logwidth, w_scratch, w_chol, out, nullptr, B, n, d, dout}, s);
+}
+
+namespace {
+// Steps per chunk of vjf_forecast_seq: the weight samples of a chunk (n dout floats per step) take at most kFcScratchBytes, and a
+// chunk is at most kFcMaxChunk steps (a roll-out launch stays on the device for milliseconds, not seconds).  VJF_FC_CHUNK (tests)
+// asks for shorter chunks.
+constexpr size_t kFcScratchBytes = (size_t)8 << 20;
+constexpr int kFcMaxChunk = 4096;
+int fc_chunk_bound(int n, int dout) {
+    const size_t per = (size_t)n * dout * 4;
+    const size_t c = kFcScratchBytes / per;
+    return c < 1 ? 1 : (c > (size_t)kFcMaxChunk ? kFcMaxChunk : (int)c);
+}
+int fc_chunk(int n, int dout) {
+    const int bound = fc_chunk_bound(n, dout);
+    const char* ce = getenv("VJF_FC_CHUNK");
+    return ce && atoi(ce) >= 1 && atoi(ce) < bound ? atoi(ce) : bound;
+}
+// (four rows of padding behind the last W[t]: a wavefront whose share of K is shorter than 4 features -- n = 37: 12, 12, 12, 1 --
+//  hands mma_tile a K < 4, whose lanes kk >= K read row kb + kk, up to n + 2, from a valid address and mask the value)
+size_t fc_scratch_bytes(int T, int n, int dout) {
+    const int bound = fc_chunk_bound(n, dout);
+    return ((size_t)(T < bound ? T : bound) * n * dout * 4 + (size_t)4 * dout * 4 + 255) / 256 * 256;
+}
+bool fc_env_on(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0 && v[0] == '0'); }
+}  // namespace
+
+int vjf_forecast_scratch_size(int32_t T, int32_t n, int32_t dout, int64_t* bytes) {
+    if (!bytes || T < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_scratch_size: bad argument");
+    *bytes = (int64_t)fc_scratch_bytes(T, n, dout);
+    return 0;
+}
+
+int vjf_forecast_seq(const float* x0, const float* u, const float* w_noise, const float* s_noise, const float* centroid,
+                     const float* logwidth, const float* w_mean, const float* w_chol, const float* tr_logvar, float* x, void* scratch,
+                     int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, void* stream) {
+    if (!x0 || !w_noise || !centroid || !logwidth || !w_mean || !w_chol || !x || !scratch) return fail(-1, "vjf_forecast_seq: null tensor");
+    if (T < 1 || B < 1 || n < 1 || dout < 1 || d < dout) return fail(-20, "vjf_forecast_seq: bad shape (T=%d B=%d n=%d d=%d dout=%d)", T, B, n, d, dout);
+    if (d > dout && !u) return fail(-21, "vjf_forecast_seq: u is required when d > dout");
+    if (s_noise && !tr_logvar) return fail(-1, "vjf_forecast_seq: state noise without tr_logvar");
+    hipStream_t s = (hipStream_t)stream;
+    const int du = d - dout;
+    if (vjf_fc_lds_floats(n, d, dout, false) * 4 > kMaxLds - 1024) return fail(-11, "vjf_forecast_seq: n=%d, d=%d too large", n, d);
+    // VJF_FC_CENTROID_LDS=0 / VJF_FC_LOOKAHEAD=0 (tests): the forms for shapes beyond the LDS / register budgets, at any shape
+    const bool cl = vjf_fc_lds_floats(n, d, dout, true) * 4 <= kMaxLds - 1024 && fc_env_on("VJF_FC_CENTROID_LDS");
+    const bool la = cl && n <= 64 * VJF_FC_KQ && dout <= 32 && fc_env_on("VJF_FC_LOOKAHEAD");
+    const size_t lds = vjf_fc_lds_floats(n, d, dout, cl) * 4, lds_w = (size_t)n * VJF_LDT * 4;
+    const int mt = (n + 15) / 16, chunk = fc_chunk(n, dout);
+    float* W = (float*)scratch;
+    allow_lds(vjf_fc_weights_kernel, lds_w);
+    for (int32_t t0 = 0; t0 < T; t0 += chunk) {
+        const int Tc = T - t0 < chunk ? T - t0 : chunk;
+        VjfFcWeightArgs wa{w_mean, w_chol, w_noise + (size_t)t0 * n * dout, W, Tc, n, dout};
+        int gy = (Tc + VJF_FC_WAVES - 1) / VJF_FC_WAVES, cap = 2048 / mt;
+        if (gy > cap) gy = cap;
+        if (gy < 1) gy = 1;
+        hipLaunchKernelGGL(vjf_fc_weights_kernel, dim3(mt, gy), dim3(VJF_FC_THREADS), lds_w, s, wa);
+        VJF_HIP(hipGetLastError());
+        VjfFcArgs a{};
+        a.x_in = t0 == 0 ? x0 : x + (size_t)t0 * B * dout;
+        a.u = u ? u + (size_t)t0 * B * du : nullptr;
+        a.e = s_noise ? s_noise + (size_t)t0 * B * dout : nullptr;
+        a.c = centroid; a.logw = logwidth; a.W = W; a.tr_logvar = tr_logvar;
+        a.x0_out = t0 == 0 ? x : nullptr;
+        a.x_out = x + (size_t)(t0 + 1) * B * dout;
+        a.Tc = Tc; a.B = B; a.n = n; a.d = d; a.dout = dout;
+        auto launch = [&](auto kernel) {
+            allow_lds(kernel, lds);
+            hipLaunchKernelGGL(kernel, dim3((B + 15) / 16), dim3(VJF_FC_THREADS), lds, s, a);
+        };
+        if (la && dout <= 16) launch(vjf_fc_rollout_kernel<1, true>);
+        else if (la) launch(vjf_fc_rollout_kernel<2, true>);
+        else if (cl) launch(vjf_fc_rollout_kernel<0, true>);
+        else launch(vjf_fc_rollout_kernel<0, false>);
+        VJF_HIP(hipGetLastError());
+    }
+    return 0;
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

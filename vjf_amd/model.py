@@ -125,6 +125,7 @@ class RBFDS(Module):
         self.add_module('velocity', LinearRegression(RBF(xdim + udim, n_rbf), xdim))
         self.register_parameter('logvar', Parameter(dev32(torch.tensor(0.), ndim2=False), requires_grad=False))
         self._n_sample = 0
+        self._fc_scratch = None
         object.__setattr__(self, '_owner', None)
 
     @property
@@ -165,6 +166,84 @@ class RBFDS(Module):
             if noise:
                 e = torch.randn(x[t + 1].shape, dtype=torch.get_default_dtype()).to(x.device, torch.float32)
                 x[t + 1] = x[t + 1] + e * s
+        return x
+
+    def _noise_mode(self) -> str:
+        o = self._owner() if self._owner is not None else None
+        return o.noise if o is not None else "reference"
+
+    def forecast_sequence(self, x0: Tensor, u: Tensor = None, n_step: int = 1, *, noise: bool = False,
+                          w_noise: Tensor = None, state_noise: Tensor = None) -> Tensor:
+        """`forecast` as ONE C-ABI call (vjf_forecast_seq): the weight samples of all steps from one batched product, then the
+        roll-out inside one kernel per chunk of steps -- what `filter_sequence` is to `filter`.  Same shapes and return type.
+        :param w_noise: (n_step, n_rbf, xdim), used in place of the per-step randn_like(w) draws
+        :param state_noise: (n_step, B, xdim), used in place of the per-step process-noise draws; implies `noise`
+        Draws that are not given follow the owning model's `noise`: "reference" draws on the CPU generator in `forecast`'s own order
+        (per step the weight draw, then the state draw), so a seed gives the same roll-out and leaves the generator where `forecast`
+        leaves it; "device" draws each tensor on the GPU in one call.  Asynchronous; reads the model's state and writes none.
+        The weight samples live in ONE scratch tensor kept on this module (like `_rls_scratch`): run one roll-out per model at a time
+        -- calls on different streams must be ordered by the caller, or go to different models."""
+        x0 = dev32(x0)
+        vel = self.velocity
+        B, dout = x0.shape
+        n, d = vel.feature.centroid.shape
+        du = d - dout
+        assert dout == vel.n_output, f"x0 has {dout} columns, expected xdim={vel.n_output}"
+        T = int(n_step)
+        assert T >= 0, 'n_step must not be negative'
+        if du > 0:
+            if u is None:
+                raise TypeError("u is required when udim > 0")
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == T, 'u must have length of n_step if present'
+            if u.ndim == 2 and B == 1:
+                u = u[:, None, :]
+            assert u.shape == (T, B, du)
+            u = u.contiguous()
+        else:
+            u = None
+        if w_noise is not None:
+            w_noise = dev32(w_noise, ndim2=False)
+            assert w_noise.shape == (T, n, dout)
+        if state_noise is not None:
+            state_noise = dev32(state_noise, ndim2=False)
+            if state_noise.ndim == 2 and B == 1:
+                state_noise = state_noise[:, None, :]
+            assert state_noise.shape == (T, B, dout)
+            state_noise = state_noise.contiguous()
+        if T == 0:
+            return x0[None].clone()
+        want_w, want_s = w_noise is None, state_noise is None and noise
+        if want_w or want_s:
+            if self._noise_mode() == "reference":          # forecast's order: per step the weight draw, then the state draw
+                # (the state draws go straight into one page-locked tensor, a contiguous slice per step -- the values and the generator
+                #  state of `randn(B, xdim)` -- and from there to the device in one copy: at 4096 trials the draws themselves are most of
+                #  the call's time, a stack of 200 tensors and a pageable copy would add half as much again)
+                dt, ws = torch.get_default_dtype(), []
+                ss = torch.empty(T, B, dout, dtype=dt, pin_memory=x0.is_cuda) if want_s else None
+                for t in range(T):
+                    if want_w:
+                        ws.append(vel._draw_weight_noise())
+                    if want_s:
+                        torch.randn(B, dout, dtype=dt, out=ss[t])
+                if want_w:
+                    w_noise = dev32(torch.stack(ws), ndim2=False)
+                if want_s:
+                    state_noise = ss.to(x0.device, torch.float32, non_blocking=True).contiguous()
+            else:
+                if want_w:
+                    w_noise = torch.randn(T, n, dout, device=x0.device, dtype=torch.float32)
+                if want_s:
+                    state_noise = torch.randn(T, B, dout, device=x0.device, dtype=torch.float32)
+        L = N.lib()
+        nbytes = ctypes.c_int64()
+        N.check(L.vjf_forecast_scratch_size(T, n, dout, ctypes.byref(nbytes)), "vjf_forecast_scratch_size")
+        if self._fc_scratch is None or self._fc_scratch.numel() < nbytes.value or self._fc_scratch.device != x0.device:   # (kept, grown on demand)
+            self._fc_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x0.device)
+        x = torch.empty(T + 1, B, dout, device=x0.device, dtype=torch.float32)
+        N.check(L.vjf_forecast_seq(N.ptr(x0), N.ptr(u), N.ptr(w_noise), N.ptr(state_noise), N.ptr(vel.feature.centroid),
+                                   N.ptr(vel.feature.logwidth), N.ptr(vel.w_mean), N.ptr(vel.w_chol), N.ptr(self.logvar), N.ptr(x),
+                                   N.ptr(self._fc_scratch), T, B, n, d, dout, stream_ptr()), "vjf_forecast_seq")
         return x
 
     @torch.no_grad()
@@ -787,5 +866,13 @@ class VJF(Module):
     def forecast(self, x0: Tensor, u: Tensor = None, n_step: int = 1, *, noise: bool = False) -> Tuple[Tensor, Tensor]:
         """vjf/model.py:321-324"""
         x = self.transition.forecast(x0, u, n_step, noise=noise)
+        y = self.decoder(x)
+        return x, y
+
+    def forecast_sequence(self, x0: Tensor, u: Tensor = None, n_step: int = 1, *, noise: bool = False,
+                          w_noise: Tensor = None, state_noise: Tensor = None) -> Tuple[Tensor, Tensor]:
+        """`forecast` with the whole horizon in one native call (RBFDS.forecast_sequence), then one decoding of all rows.
+        :return: x (n_step + 1, B, xdim), y (n_step + 1, B, ydim)"""
+        x = self.transition.forecast_sequence(x0, u, n_step, noise=noise, w_noise=w_noise, state_noise=state_noise)
         y = self.decoder(x)
         return x, y
