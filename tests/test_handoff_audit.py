@@ -24,7 +24,7 @@ def test_every_plain_load_of_the_resident_kernels_is_certified(tmp_path):
     for k in mod.KERNELS:
         assert counts[k][0] > 100, (k, counts[k])          # (the kernels are there and their hand-off loads are sc1)
     # the audit does find what it is for: an uncertified line is reported
-    key = ("vjf_mega_kernel.h", "grp = A.sl_grp[quad];")
+    key = ("vjf_mega_sgd.h", "grp = A.sl_grp[quad];")
     why = mod.ALLOW.pop(key)
     try:
         _, _, bad2 = mod.audit(asm)

@@ -1,4 +1,4 @@
-// Diagnostic micro-benchmark (not part of the product): the trial role's LDS-fed product out^T = W x^T (vjf_mega_kernel.h: mg_mma2_lds)
+// Diagnostic micro-benchmark (not part of the product): the trial role's LDS-fed product out^T = W x^T (vjf_mega_common.h: mg_mma2_lds)
 // for one recognition layer of config B -- W (128, 70) and 32 trials' activations in LDS, 8 wavefronts, one 16-row tile each, two
 // 16-trial column groups -- in the variants below, one workgroup of 512 threads per compute unit, R repetitions.
 //   hipcc -O3 --offload-arch=gfx950 -o tools/lds_mma_bench tools/lds_mma_bench.hip && tools/lds_mma_bench
