@@ -106,6 +106,8 @@ enum vjf_scalar {
     VJF_SC_STATUS = 7,     /* status bits as an integer-valued float */
     VJF_SC_TRI_CLEAN = 8,  /* device-internal: 1 once the zero halves of w_chol / w_pchol have been cleared;
                               write 0 after storing a dense matrix into either tensor from the host */
+    VJF_SC_SHRINK = 9,     /* velocity.rls forgetting factor  module.py:80-96; a stored 0 reads as 1 (every state written
+                              before the slot had a meaning is zero there) */
     VJF_N_SCALARS = 16
 };
 

@@ -66,16 +66,20 @@ ALLOW = {
     ("vjf_mega_sgd.h", "if (sw == 0 && tid == 0 && mode_rls && SC[VJF_SC_TRI_CLEAN] == 0.f) {"): "own: written by this lane alone, at the end of a launch",
     # ---- vjf_post_kernel.h
     ("vjf_post_kernel.h", "s_x[r * LX + c] = (r < n && c < dz) ? Wold[(size_t)r * dz + c] : 0.f;"): "acq: the failed-factorisation path acquires before it reads the state",
-    ("vjf_post_kernel.h", "for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, fmaf(-G[e], inv_v, Pm[e]));"): "acq: same path",
+    ("vjf_post_kernel.h", "const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);"):
+        "const: the forgetting factor, set by the host between launches (and behind the same path's acquire)",
+    ("vjf_post_kernel.h", "for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));"): "acq: same path",
     ("vjf_post_kernel.h", "vjf_store_wt(A.xt + (size_t)j * n + k, Wc[e]);"): "const: w_chol as the launch found it (the launch's first act)",
     # ---- vjf_chol_kernel.h (vjf_chol_body is shared with the per-step kernels)
     ("vjf_chol_kernel.h", "float sig = S[P.off[VJF_SLOT_TR_LOGVAR]];"): "const: the value the launch found; from the second step on it is replaced by the hand-off word's",
+    ("vjf_chol_kernel.h", "const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);"):
+        "const: the forgetting factor, set by the host between launches (no role of a launch writes that word)",
     ("vjf_chol_kernel.h", "return *reinterpret_cast<const float4*>(G + (size_t)gi * n + gj);"): "other: !A.stat_count (per-step kernels: a kernel boundary lies before)",
     ("vjf_chol_kernel.h", "if (sp && !it_src_state) v[q] = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);"): "own: this workgroup's copy of P of the step before",
     ("vjf_chol_kernel.h", "else v[q] = (gi < n && gj < n) ? *reinterpret_cast<const float4*>(Pm + (size_t)gi * n + gj) : pad4(gi, gj);"):
         "const: the state's P at the first step of a launch, before the operand role may overwrite it (the 'operands loaded' word follows these loads)",
     ("vjf_chol_kernel.h", "s_g[e] = (r < n && j < dz) ? A.gbuf[(size_t)r * dz + j] : 0.f;"): "other: !A.post",
-    ("vjf_chol_kernel.h", "if (!sp) for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) Pm[e] = fmaf(-G[e], inv_v, Pm[e]);"): "other: !self_prep",
+    ("vjf_chol_kernel.h", "if (!sp) for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) Pm[e] = __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam);"): "other: !self_prep",
     ("vjf_chol_kernel.h", "float4 pv = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);"): "own: this workgroup's copy of P",
     ("vjf_chol_kernel.h", "if (!A.no_triclean && SC[VJF_SC_TRI_CLEAN] == 0.f) {"): "other: the resident loop sets no_triclean",
     ("vjf_chol_kernel.h", "if (SC[VJF_SC_TRI_CLEAN] == 0.f) {"): "other: !A.post",

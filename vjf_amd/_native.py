@@ -26,7 +26,7 @@ SLOT_MEAN_W, SLOT_LV_W, SLOT_LV_B, SLOT_DEC_W, SLOT_DEC_B = 22, 23, 24, 25, 26
 SLOT_W_MEAN, SLOT_W_CHOL, SLOT_W_PREC, SLOT_W_PCHOL, SLOT_SCALARS = 27, 28, 29, 30, 31
 N_SLOTS = 32
 # enum vjf_scalar
-SC_N_LIK, SC_N_TR, SC_LR_LIK, SC_LR_DEC, SC_LR_TR, SC_LR_REC, SC_FREEZE_DEC, SC_STATUS, SC_TRI_CLEAN = range(9)
+SC_N_LIK, SC_N_TR, SC_LR_LIK, SC_LR_DEC, SC_LR_TR, SC_LR_REC, SC_FREEZE_DEC, SC_STATUS, SC_TRI_CLEAN, SC_SHRINK = range(10)
 N_SCALARS = 16
 
 

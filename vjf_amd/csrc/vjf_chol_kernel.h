@@ -70,17 +70,18 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
         __shared__ float s_part[4 * 32];
         const int n = P.n, dz = P.dz, i = bid;
         const float inv_v = expf(-S[P.off[VJF_SLOT_TR_LOGVAR]]);
+        const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);
         float* Pm = S + P.off[VJF_SLOT_W_PREC];
         const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
         const float* G = A.red + P.red_G;
         const float* FDX = A.red + P.red_FDX;
-        // g[i][:] = sum_k P[i][k] W[k][:] : thread k (n <= 224 < 256 on this path) holds one term per output,
+        // g[i][:] = sum_k lambda P[i][k] W[k][:] : thread k (n <= 224 < 256 on this path) holds one term per output,
         // then wave + workgroup reduction
         const int k = tid;
         float p = 0.f;
         if (k < n) {
-            p = Pm[(size_t)i * n + k];
-            Pm[(size_t)i * n + k] = p + G[(size_t)i * n + k] * inv_v;      // P += Phi^T Phi / v (module.py:96)
+            p = vjf_lam_mul(Pm[(size_t)i * n + k], lam);                   // lambda P: of the update and of g = (lambda P) W
+            Pm[(size_t)i * n + k] = p + G[(size_t)i * n + k] * inv_v;      // P = lambda P + Phi^T Phi / v (module.py:96)
         }
         for (int j = 0; j < dz; ++j) {
             float v = (k < n) ? p * Wm[(size_t)k * dz + j] : 0.f;
@@ -162,8 +163,9 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
 
 // ---------------------------------------------------------------------------------------------
 // RLS operands, 16 rows of P per workgroup (replaces the row part of vjf_prep_kernel on the fast path):
-//   g[i][:] = sum_k P[i][k] W[k][:] + (Phi^T dx)[i][:] / v     (module.py:94)   on v_mfma_f32_16x16x4_f32, K split over 4 wavefronts
-//   P[i][:] += (Phi^T Phi)[i][:] / v                            (module.py:96)   on the rows just read
+//   g[i][:] = sum_k lambda P[i][k] W[k][:] + (Phi^T dx)[i][:] / v   (module.py:94)   on v_mfma_f32_16x16x4_f32, K split over 4 wavefronts
+//   P[i][:] = lambda P[i][:] + (Phi^T Phi)[i][:] / v                 (module.py:96)   on the rows just read
+// (lambda: the forgetting factor, VJF_SC_SHRINK; the rows are scaled once, as they arrive)
 // grid = ceil(n / 16) workgroups of 256 threads; n % 4 == 0.
 #define VJF_PREPG_LDP(n) ((n) + 4)
 static inline size_t vjf_prepg_lds_bytes(const VjfPlan& P) { return ((size_t)16 * VJF_PREPG_LDP(P.n) + (size_t)P.n * 17 + 4 * 16 * 17) * 4; }
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
     if (!do_upd || warm) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = P.n, dz = P.dz, i0 = blockIdx.x * 16, ldp = VJF_PREPG_LDP(n);
-    float* s_p = lds;                                  // [16][n + 4]  rows of P before the update
+    float* s_p = lds;                                  // [16][n + 4]  rows of lambda P (P before the update)
     float* s_w = s_p + 16 * ldp;                       // [n][17]      W, columns dz..15 zero
     float* s_r = s_w + (size_t)n * 17;                 // [4][16][17]  per-wavefront partial products
     float* S = A.state;
@@ -193,6 +195,7 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
     }
     // (a vector load that bypasses L1 / the scalar cache: sigma may have been written while this kernel was already waiting)
     const float inv_v = expf(-__hip_atomic_load(S + P.off[VJF_SLOT_TR_LOGVAR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);
     float* Pm = S + P.off[VJF_SLOT_W_PREC];
     const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
     const float* G = A.red + P.red_G;
@@ -207,6 +210,11 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
             const size_t off = in ? (size_t)(i0 + row) * n + c4 : 0;
             p[q] = *reinterpret_cast<const float4*>(Pm + off);
             g[q] = *reinterpret_cast<const float4*>(G + off);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            p[q].x = vjf_lam_mul(p[q].x, lam); p[q].y = vjf_lam_mul(p[q].y, lam);
+            p[q].z = vjf_lam_mul(p[q].z, lam); p[q].w = vjf_lam_mul(p[q].w, lam);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -737,6 +745,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     const float* G = it_red + P.red_G;
     const float* FDX = it_red + P.red_FDX;
     float sig = S[P.off[VJF_SLOT_TR_LOGVAR]];
+    const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);
     const float Bf = (float)A.B_total;
     unsigned st = 0;
     const bool sp = A.post && A.self_prep;
@@ -776,7 +785,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             return make_float4(gi == gj ? 1.f : 0.f, gi == gj + 1 ? 1.f : 0.f, gi == gj + 2 ? 1.f : 0.f, gi == gj + 3 ? 1.f : 0.f);
         };
         // self_prep: every thread first issues its loads of P_old (pscr) and of G, then the workgroup waits for sigma of the
-        // previous step, and P_new = P_old + G / v is formed in the registers (fmaf, as vjf_prepg_kernel forms the state's P).
+        // previous step, and P_new = lambda P_old + G / v is formed in the registers (as vjf_prepg_kernel forms the state's P).
         // Either way the blocks of P_new go to pscr for the next step's kernel.
         bool lscr_guard = false;                                        // the post workgroups' exit count is still to be checked
         auto sigma_wait = [&]() {
@@ -847,10 +856,13 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         if (sp) {
             sigma_wait();
             const float inv_v = expf(-sig);
+            // (the identity padding of the last block is scaled too and decays as lambda^t in pscr within a launch: harmless --
+            //  the diagonal chain skips the padded rounds (n % 4 == 0) and writes identity into the factor there, and the
+            //  roll-back touches entries inside the matrix only)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                v[q].x = fmaf(g[q].x, inv_v, v[q].x); v[q].y = fmaf(g[q].y, inv_v, v[q].y);
-                v[q].z = fmaf(g[q].z, inv_v, v[q].z); v[q].w = fmaf(g[q].w, inv_v, v[q].w);
+                v[q].x = fmaf(g[q].x, inv_v, vjf_lam_mul(v[q].x, lam)); v[q].y = fmaf(g[q].y, inv_v, vjf_lam_mul(v[q].y, lam));
+                v[q].z = fmaf(g[q].z, inv_v, vjf_lam_mul(v[q].z, lam)); v[q].w = fmaf(g[q].w, inv_v, vjf_lam_mul(v[q].w, lam));
             }
         }
 #pragma unroll
@@ -1047,12 +1059,12 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         VJF_STAMP(2);
         if (!ok) {
             // Reference: the fallback calls the removed torch.eig and raises (module.py:104-112).  Here:
-            // undo P += G / v (exact up to one rounding) and leave W, w_chol, w_pchol as they were.
+            // undo P = lambda P + G / v (to rounding: (P' - G / v) / lambda) and leave W, w_chol, w_pchol as they were.
             st |= VJF_STATUS_RLS_FAILED;
             const float inv_v = expf(-sig);
             // (self_prep: the state's P is in the hands of the operand kernel on the post kernel's stream; that kernel's y / W
             //  workgroup, which follows it there, takes the update back)
-            if (!sp) for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) Pm[e] = fmaf(-G[e], inv_v, Pm[e]);
+            if (!sp) for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) Pm[e] = __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam);
             if (A.post) {
                 for (int idx = tid; idx < ntri * 256; idx += VJF_CHOL_THREADS) {   // the copy for the next kernel, likewise
                     const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
@@ -1061,6 +1073,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                         float4 pv = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);
                         const float4 gv = g4(gi, gj);          // (another role's stores on the one-launch route: an sc1 load there, found by tools/audit_plain_loads.py)
                         pv.x = fmaf(-gv.x, inv_v, pv.x); pv.y = fmaf(-gv.y, inv_v, pv.y); pv.z = fmaf(-gv.z, inv_v, pv.z); pv.w = fmaf(-gv.w, inv_v, pv.w);
+                        pv.x = __fdiv_rn(pv.x, lam); pv.y = __fdiv_rn(pv.y, lam); pv.z = __fdiv_rn(pv.z, lam); pv.w = __fdiv_rn(pv.w, lam);
                         *reinterpret_cast<float4*>(A.pscr + (size_t)idx * 4) = pv;
                     }
                 }

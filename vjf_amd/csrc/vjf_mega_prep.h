@@ -3,12 +3,12 @@
 #include "vjf_mega_common.h"
 
 // ------------------------------------------------------------------------------------------------ operand role
-// g = P W + Phi^T dx / v and P += Phi^T Phi / v for 16 rows (module.py:94-96); Phi^T dx = sum of the trial workgroups' early slabs
+// g = lambda P W + Phi^T dx / v and P = lambda P + Phi^T Phi / v for 16 rows (module.py:94-96); Phi^T dx = sum of the trial workgroups' early slabs
 __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArgs& A, float* lds, const int pw) {
     constexpr int NT = VJF_MG_THREADS, NW = VJF_MG_WAVES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = P.n, dz = P.dz, i0 = pw * 16, ldp = VJF_PREPG_LDP(n);
-    float* s_p = lds;                                  // [16][n + 4]  rows of P before the update
+    float* s_p = lds;                                  // [16][n + 4]  rows of lambda P (P before the update)
     float* s_w = s_p + 16 * ldp;                       // [n][17]      W, columns dz..15 zero
     float* s_r = s_w + (size_t)n * 17;                 // [NW][16][17] per-wavefront partial products
     float* s_f = s_r + NW * 16 * 17;                   // [16][17]     Phi^T dx rows
@@ -72,6 +72,7 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
             }
         }
         const float inv_v = expf(-mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]));
+        const float lam = vjf_shrink_of(mg_ld(SCW + VJF_SC_SHRINK));
         float* Pm = S + P.off[VJF_SLOT_W_PREC];
         const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
         const float* G = red + P.red_G;
@@ -87,6 +88,11 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
                 const size_t off = in ? (size_t)(i0 + row) * n + c4 : 0;
                 p[q] = mg_ld4(r_P, (int)off);                                  // (P: this workgroup's own rows -- and the y / W loop's after a failed factorisation)
                 g[q] = mg_ld4(r_G, (int)off);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                                      // lambda P: what the update adds to, and the P of g = (lambda P) W
+                p[q].x = vjf_lam_mul(p[q].x, lam); p[q].y = vjf_lam_mul(p[q].y, lam);
+                p[q].z = vjf_lam_mul(p[q].z, lam); p[q].w = vjf_lam_mul(p[q].w, lam);
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {

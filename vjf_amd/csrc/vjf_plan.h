@@ -265,6 +265,11 @@ __device__ __forceinline__ bool vjf_wg_wait_sc1(const unsigned* count, unsigned 
     __syncthreads();
     return there;
 }
+// The forgetting factor of the RLS update as the scalar slot holds it: 0 (a state from before the slot had a meaning) is 1.
+__device__ __forceinline__ float vjf_shrink_of(float stored) { return stored == 0.f ? 1.0f : stored; }
+// lambda p, rounded on its own: the sums and fmaf it feeds keep the form (and, at lambda = 1, the bits) they had without it --
+// the empty statement keeps the compiler from contracting the product into them
+__device__ __forceinline__ float vjf_lam_mul(float p, float lam) { float r = p * lam; asm("" : "+v"(r)); return r; }
 __device__ __forceinline__ void vjf_store_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // returns false (lane 0 only; the others get true) when the count did not arrive within the bound
 __device__ __forceinline__ bool vjf_wg_wait(const unsigned* count, unsigned target, int tid, const float* status = nullptr) {

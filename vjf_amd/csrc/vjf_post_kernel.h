@@ -507,13 +507,14 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 s_x[r * LX + c] = (r < n && c < dz) ? Wold[(size_t)r * dz + c] : 0.f;
             }
             prefetch_tail();                                   // (the failure may have come before the first column)
-            if (A.undo_P) {                                    // exact up to one rounding, as the Cholesky kernel does on its own path
+            if (A.undo_P) {                                    // (P' - G / v) / lambda, as the Cholesky kernel does on its own path
                 float* Pm = A.state + P.off[VJF_SLOT_W_PREC];
                 const float* G = it_red + P.red_G;
                 const float inv_v = expf(-S[P.off[VJF_SLOT_TR_LOGVAR]]);
+                const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);
                 // (write-through: in the one-launch route the next step's operand workgroups, on other CUs, read these rows
                 //  with no kernel boundary in between)
-                for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, fmaf(-G[e], inv_v, Pm[e]));
+                for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));
             }
         }
         __syncthreads();

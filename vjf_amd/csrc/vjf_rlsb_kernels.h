@@ -75,14 +75,15 @@ __global__ __launch_bounds__(256) void vjf_rlsb_prep_kernel(VjfPlan P, VjfRlsbAr
     const int n = P.n, dz = P.dz;
     float* S = A.state;
     const float inv_v = expf(-S[P.off[VJF_SLOT_TR_LOGVAR]]);
+    const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);
     const float* Pm = S + P.off[VJF_SLOT_W_PREC];
     float* Lm = A.Lw;
     const float* G = A.red + P.red_G;
     const float* FDX = A.red + P.red_FDX;
     const int gid = blockIdx.x * 256 + threadIdx.x, gsz = gridDim.x * 256;
     if (gid == 0) { A.ok[0] = 1; A.ok[4] = 0; }             // (ok[4]: the step counter of vjf_rlsc_loop_kernel)
-    for (int e = gid; e < n * dz; e += gsz) A.gbuf[e] = A.gbuf[e] + FDX[e] * inv_v;   // gbuf holds P W (the GEMM before this kernel)
-    for (int e = gid; e < n * n; e += gsz) Lm[e] = Pm[e] + G[e] * inv_v;
+    for (int e = gid; e < n * dz; e += gsz) A.gbuf[e] = vjf_lam_mul(A.gbuf[e], lam) + FDX[e] * inv_v;   // gbuf holds P W (the GEMM before this kernel)
+    for (int e = gid; e < n * n; e += gsz) Lm[e] = vjf_lam_mul(Pm[e], lam) + G[e] * inv_v;
 }
 
 // One block column of the factorisation and one block row of the inverse per launch (left-looking, so that a column needs ONE
@@ -357,7 +358,7 @@ __global__ __launch_bounds__(VJF_RLSC_THREADS) void vjf_rlsc_loop_kernel(VjfPlan
     }
 }
 
-// w_chol = X^T (module.py:102), zero halves of w_chol / w_pchol, P += Phi^T Phi / v; after a failed pivot only the status bit
+// w_chol = X^T (module.py:102), zero halves of w_chol / w_pchol, P = lambda P + Phi^T Phi / v; after a failed pivot only the status bit
 // (the reference's fallback calls the removed torch.eig and raises, module.py:104-112: the RLS state stays as it was)
 __global__ __launch_bounds__(256) void vjf_rlsb_final_kernel(VjfPlan P, VjfRlsbArgs A) {
     const int n = P.n;
@@ -369,6 +370,7 @@ __global__ __launch_bounds__(256) void vjf_rlsb_final_kernel(VjfPlan P, VjfRlsbA
         return;
     }
     const float inv_v = expf(-S[P.off[VJF_SLOT_TR_LOGVAR]]);
+    const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);
     float* Pm = S + P.off[VJF_SLOT_W_PREC];
     float* Wc = S + P.off[VJF_SLOT_W_CHOL];
     float* Lm = S + P.off[VJF_SLOT_W_PCHOL];
@@ -378,6 +380,6 @@ __global__ __launch_bounds__(256) void vjf_rlsb_final_kernel(VjfPlan P, VjfRlsbA
         Wc[e] = (j >> 5) >= (i >> 5) ? A.X[(size_t)j * n + i] : 0.f;
         const int bi = i >> 5, bj = j >> 5;                        // w_pchol = L (module.py:99-100)
         Lm[e] = bj > bi ? 0.f : bj == bi ? A.Ld[(size_t)bi * 1024 + (i & 31) * 32 + (j & 31)] : A.Lw[e];
-        Pm[e] += G[e] * inv_v;
+        Pm[e] = vjf_lam_mul(Pm[e], lam) + G[e] * inv_v;
     }
 }

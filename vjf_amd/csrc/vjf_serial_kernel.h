@@ -211,6 +211,9 @@ __device__ __forceinline__ void vjf_trinv_blocked(const float* L, float* X, floa
 // FDX = Phi^T target:  g = shrink P W + FDX / v ;  P = shrink P + G / v ;  L = chol(P) ;
 // W = P^-1 g ;  w_chol = L^-T.  work: X (n*n) | g (n*dz) | y (n*dz) | Dinv.  All threads call.
 // Returns 0, or VJF_STATUS_RLS_FAILED with P, W, w_chol, L left as they were.
+// APART (the fused step): shrink x is rounded on its own, so that at shrink = 1 the sums keep the bits they had when the step
+// passed the constant 1; the stand-alone operator keeps its own form.
+template <bool APART = false>
 __device__ __forceinline__ unsigned vjf_rls_device(int n, int dz, float inv_v, float shrink, float* Pm, float* Wm, float* Wc, float* Lm,
                                    const float* G, const float* FDX, float* work, float* lds) {
     const int tid = threadIdx.x;
@@ -222,21 +225,22 @@ __device__ __forceinline__ unsigned vjf_rls_device(int n, int dz, float inv_v, f
         const int i = e / dz, j = e - i * dz;
         float acc = 0.f;
         for (int k = 0; k < n; ++k) acc = fmaf(Pm[(size_t)i * n + k], Wm[(size_t)k * dz + j], acc);
-        gbuf[e] = acc * shrink + FDX[e] * inv_v;
+        gbuf[e] = APART ? vjf_lam_mul(acc, shrink) + FDX[e] * inv_v : acc * shrink + FDX[e] * inv_v;
     }
     // Factor P_new in place in the w_pchol buffer.  If a pivot fails, the reference's fallback
     // (module.py:104-112) calls the removed torch.eig and raises; here the second pass of the loop
     // restores L = chol(P_old), the RLS state stays as it was and the failure is reported.
     bool failed = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        for (int e = tid; e < n * n; e += VJF_K2_THREADS) Lm[e] = attempt == 0 ? Pm[e] * shrink + G[e] * inv_v : Pm[e];
+        for (int e = tid; e < n * n; e += VJF_K2_THREADS)
+            Lm[e] = attempt != 0 ? Pm[e] : APART ? vjf_lam_mul(Pm[e], shrink) + G[e] * inv_v : Pm[e] * shrink + G[e] * inv_v;
         __syncthreads();
         if (vjf_chol_blocked(Lm, n, lds)) break;
         failed = true;
         __syncthreads();
     }
     if (failed) return VJF_STATUS_RLS_FAILED;
-    for (int e = tid; e < n * n; e += VJF_K2_THREADS) Pm[e] = Pm[e] * shrink + G[e] * inv_v;
+    for (int e = tid; e < n * n; e += VJF_K2_THREADS) Pm[e] = APART ? vjf_lam_mul(Pm[e], shrink) + G[e] * inv_v : Pm[e] * shrink + G[e] * inv_v;
     vjf_trinv_blocked(Lm, X, Dinv, n, lds);
     for (int e = tid; e < n * dz; e += VJF_K2_THREADS) {                      // y = X g
         const int r = e / dz, j = e - r * dz;
@@ -430,7 +434,7 @@ __global__ __launch_bounds__(VJF_K2_THREADS) void vjf_serial_kernel(VjfPlan P, V
     const float* FDX = A.red + P.red_FDX;
     if (do_upd) {
         if (!warm)                                              // LinearRegression.rls, module.py:79-102
-            st |= vjf_rls_device(n, dz, expf(-sig), 1.0f, Pm, Wm, Wc, Lm, G, FDX, A.work, lds);
+            st |= vjf_rls_device<true>(n, dz, expf(-sig), vjf_shrink_of(SC[VJF_SC_SHRINK]), Pm, Wm, Wc, Lm, G, FDX, A.work, lds);
         // residual mean square with the (possibly new) W, fp64 accumulation
         double part = 0.0;
         if (A.E) {

@@ -120,13 +120,17 @@ class _ExponentialLR:
 
 class RBFDS(Module):
     """RBF dynamical system  x[t] = x[t-1] + Phi([x[t-1], u[t]]) W    (vjf/model.py:327-391)"""
-    def __init__(self, n_rbf: int, xdim: int, udim: int):
+    def __init__(self, n_rbf: int, xdim: int, udim: int, shrink: float = 1.):
+        """:param shrink: forgetting factor of the RLS update, 0 < shrink <= 1, 1 meaning no forgetfulness (vjf/module.py:80-96;
+        the reference's step hard-codes 1, vjf/model.py:371)"""
         super().__init__()
         self.add_module('velocity', LinearRegression(RBF(xdim + udim, n_rbf), xdim))
         self.register_parameter('logvar', Parameter(dev32(torch.tensor(0.), ndim2=False), requires_grad=False))
         self._n_sample = 0
         self._fc_scratch = None
         object.__setattr__(self, '_owner', None)
+        self._shrink = 1.
+        self.shrink = shrink
 
     @property
     def n_sample(self):
@@ -140,6 +144,25 @@ class RBFDS(Module):
             o._set_counter("tr", v)
         else:
             self._n_sample = v
+
+    @property
+    def shrink(self) -> float:
+        """Forgetting factor of the RLS update: P <- shrink P + Phi'Phi / v in every step that runs it (fused or operator by
+        operator).  May be set between calls: the write is ordered on the current stream like the learning rates and holds from the
+        next call on; the native context stays."""
+        o = self._owner() if self._owner is not None else None
+        return o._get_shrink() if o is not None else self._shrink
+
+    @shrink.setter
+    def shrink(self, v):
+        v = float(v)
+        if not 0. < v <= 1.:                        # (NaN fails both comparisons)
+            raise ValueError(f"shrink must be in (0, 1], got {v}")
+        o = self._owner() if self._owner is not None else None
+        if o is not None:
+            o._set_shrink(v)
+        else:
+            self._shrink = v
 
     def forward(self, x: Tensor, u: Tensor = None, sampling: bool = True, leak: float = 0., noise: Tensor = None):
         x = dev32(x)
@@ -254,7 +277,7 @@ class RBFDS(Module):
         xu = nonecat(xs, None if ut is None else dev32(ut))
         dx = xt - xs
         if not warm_up:
-            self.velocity.rls(xu, dx, self.logvar.exp(), shrink=1.)
+            self.velocity.rls(xu, dx, self.logvar.exp(), shrink=self.shrink)
         residual = dx - self.velocity(xu, sampling=False).mean
         mse = residual.pow(2).mean()
         var, n_sample = running_var(self.logvar.exp(), self.n_sample, mse, xs.shape[0], size_cap=500)
@@ -278,7 +301,7 @@ class RBFDS(Module):
 
 class VJF(Module):
     def __init__(self, ydim: int, xdim: int, likelihood: Module, transition: Module, recognition: Module,
-                 *, lr: float = 1e-4, lr_decay: float = .9, noise: str = "reference"):
+                 *, lr: float = 1e-4, lr_decay: float = .9, noise: str = "reference", shrink: float = None):
         """
         Use VJF.make_model   (vjf/model.py:50-78)
         :param likelihood: GLM likelihood, Gaussian or Poisson
@@ -286,6 +309,8 @@ class VJF(Module):
         :param recognition: y[t], f(x[t-1], u[t]) -> x[t]
         :param lr_decay: multiplicative factor of learning rate decay
         :param noise: "reference" (CPU generator, reference draw order) or "device"
+        :param shrink: forgetting factor of the transition's RLS update, 0 < shrink <= 1 (`transition.shrink`; None keeps the
+                       transition's own, which is 1 -- no forgetfulness, the reference's step -- unless it was built otherwise)
         """
         super().__init__()
         self.add_module('likelihood', likelihood)
@@ -300,6 +325,8 @@ class VJF(Module):
         if noise not in ("reference", "device"):
             raise ValueError("noise must be 'reference' or 'device'")
         self.noise = noise
+        if shrink is not None:
+            transition.shrink = shrink
         self.ydim, self.xdim = ydim, xdim
         feat = transition.velocity.feature
         self.udim = feat.centroid.shape[1] - xdim
@@ -364,6 +391,7 @@ class VJF(Module):
         self._scalars = self._blob[off[N.SLOT_SCALARS]:off[N.SLOT_SCALARS] + N.N_SCALARS]
         self._scalars[N.SC_N_LIK] = float(getattr(self.likelihood, "_n_sample", 0))
         self._scalars[N.SC_N_TR] = float(self.transition._n_sample)
+        self._scalars[N.SC_SHRINK] = float(getattr(self.transition, "_shrink", 1.))
         self._push_lr(force=True)
 
     def _get_counter(self, which):
@@ -371,6 +399,13 @@ class VJF(Module):
 
     def _set_counter(self, which, v):
         self._scalars[N.SC_N_LIK if which == "lik" else N.SC_N_TR] = float(v)
+
+    def _get_shrink(self):
+        v = float(self._scalars[N.SC_SHRINK].item())
+        return v if v != 0. else 1.                  # (a stored 0 reads as 1, on the device too: include/vjf_hip.h)
+
+    def _set_shrink(self, v):
+        self._scalars[N.SC_SHRINK] = float(v)
 
     def _push_lr(self, force=False):
         lrs = [float(g['lr']) for g in self.optimizer.param_groups]
@@ -408,7 +443,9 @@ class VJF(Module):
     def get_state(self) -> dict:
         """Everything a run needs to resume, as numpy arrays: the 13 `state_dict` tensors, the RLS tensors of
         `transition.velocity` (plain attributes in the reference: vjf/module.py:45-54), the two sample counters, the
-        four group learning rates, the decoder-freeze flag and the shape of the model."""
+        four group learning rates, the decoder-freeze flag and the shape of the model -- and, where it is not 1, the forgetting
+        factor of the RLS update as `"transition.shrink"`.  The format rule: an absent key means 1 (`set_state`), so a state at the
+        default has the keys it had before the factor existed and older states load unchanged."""
         import numpy as np
         self.check_status()                  # (raises if a device-side wait of an earlier call timed out: that state is not one to keep)
         st = {k: v.detach().cpu().numpy().copy() for k, v in self.state_dict().items()}
@@ -417,6 +454,8 @@ class VJF(Module):
             st["transition.velocity." + k] = getattr(lr, k).detach().cpu().numpy().copy()
         st["likelihood.n_sample"] = np.int64(self._get_counter("lik"))
         st["transition.n_sample"] = np.int64(self._get_counter("tr"))
+        if self._get_shrink() != 1.:         # (1, no forgetting, is what a state without the key means: such a state keeps the
+            st["transition.shrink"] = np.float64(self._get_shrink())                     #  format it had before the factor)
         st["optimizer.lr"] = np.array([float(g["lr"]) for g in self.optimizer.param_groups], np.float64)
         st["decoder.frozen"] = np.int64(int(self._scalars[N.SC_FREEZE_DEC].item() != 0))
         st["config"] = np.array([self.ydim, self.xdim, self.udim, self.n_rbf, self._lik] + list(self.hidden_sizes), np.int64)
@@ -430,6 +469,9 @@ class VJF(Module):
         mine = [self.ydim, self.xdim, self.udim, self.n_rbf, self._lik] + list(self.hidden_sizes)
         if cfg != mine:
             raise ValueError(f"state is for a model of shape {cfg}, this one is {mine}")
+        shrink = float(st["transition.shrink"]) if "transition.shrink" in st else 1.   # (a state from before the key: no forgetting)
+        if not 0. < shrink <= 1.:
+            raise ValueError(f"shrink must be in (0, 1], got {shrink}")
         own = self.state_dict()
         with torch.no_grad():
             for k, v in own.items():
@@ -440,6 +482,7 @@ class VJF(Module):
                 t.copy_(torch.as_tensor(np.asarray(st["transition.velocity." + k]), dtype=torch.float32).reshape(t.shape))
         self._set_counter("lik", int(st["likelihood.n_sample"]))
         self._set_counter("tr", int(st["transition.n_sample"]))
+        self.transition.shrink = shrink
         for g, v in zip(self.optimizer.param_groups, np.asarray(st["optimizer.lr"]).tolist()):
             g["lr"] = float(v)
         self._push_lr(force=True)
