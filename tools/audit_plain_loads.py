@@ -26,8 +26,8 @@ KERNELS = ("_Z15vjf_mega_kernel", "_Z20vjf_mega_lite_kernel", "_Z20vjf_rlsc_loop
 CONST_SYMBOLS = ("vjf_host_mirror", "vjf_chaos_range", "vjf_chaos_base")
 
 ALLOW = {
-    # ---- vjf_plan.h
-    ("vjf_plan.h", "unsigned old = *u, assumed;"): "own: the first guess of a compare-and-swap loop (a stale guess costs one more round)",
+    # ---- vjf_handoff.h
+    ("vjf_handoff.h", "unsigned old = *u, assumed;"): "own: the first guess of a compare-and-swap loop (a stale guess costs one more round)",
     # ---- the one-launch route: mg_stage_centres (vjf_mega_common.h; trial, moments and Gram roles), then the trial and Gram roles
     ("vjf_mega_common.h", "for (int e = tid; e < npad * dxu; e += NT) { const int c = e / npad, k = e - c * npad; s_cen[e] = k < n ? cen[k * dxu + c] : 0.f; }"): "const: centroids",
     ("vjf_mega_common.h", "for (int e = tid; e < npad; e += NT) { float v = 0.f; if (e < n) { const float w = expf(lw[e]); v = -0.5f / (w * w); } s_iw[e] = v; }"): "const: widths",
@@ -40,23 +40,23 @@ ALLOW = {
     ("vjf_mega_trial.h", "const float bf = tl ? ((mg_lds_cf*)bias_l)[f] : ((mg_glb_cf*)bias_g)[f];"): "acq: LDS when the parameters are staged; else the state, behind the gate's acquire (!tl)",
     ("vjf_mega_trial.h", "if (f < dz) s_mu[f * LD + b] = v; else s_lv[(f - dz) * LD + b] = v + (tl ? ((mg_lds_cf*)bl_l)[f - dz] : ((mg_glb_cf*)bl_g)[f - dz]);"): "acq: as the layer biases",
     ("vjf_mega_trial.h", "if (f < dy) { const float df = tl ? ((mg_lds_cf*)d_l)[f] : ((mg_glb_cf*)d_g)[f]; s_py[f * LD + (lane & 15)] = acc0[r] + df; s_py[f * LD + 16 + (lane & 15)] = acc1[r] + df; }"): "acq: as the layer biases",
-    ("vjf_mega_gram.h", "const float m = mu_s ? mg_ld(mu_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_MEAN] + c2];   // (sc1: no acquire"): "const: the prior (the posterior is an sc1 load)",
-    ("vjf_mega_gram.h", "const float l = mu_s ? mg_ld(lv_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c2]; //  behind the waits)"): "const: the prior",
+    ("vjf_mega_gram.h", "const float m = mu_s ? vjf_ld_sc1(mu_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_MEAN] + c2];   // (sc1: no acquire"): "const: the prior (the posterior is an sc1 load)",
+    ("vjf_mega_gram.h", "const float l = mu_s ? vjf_ld_sc1(lv_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c2]; //  behind the waits)"): "const: the prior",
     ("vjf_mega_gram.h", "v = fmaf(eps_s[(size_t)b * dz + c2], expf(0.5f * l), m);"): "const: the noise input",
     ("vjf_mega_gram.h", "v = u_e[(size_t)b * du + c2 - dz];"): "const: the control input",
-    # ---- moments role (its L^-1 loads: mg_ld4_plain, vjf_mega_common.h), image builders (launches without an RLS update)
-    ("vjf_mega_common.h", "const mg_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, float_index * 4, 0, 0);"):
-        "own: mg_ld4_plain -- used for L^-1 of a launch WITHOUT an RLS update only (mg_varN): written once at the start of the launch, "
+    # ---- moments role (its L^-1 loads: vjf_ld4_plain, vjf_handoff.h), image builders (launches without an RLS update)
+    ("vjf_handoff.h", "const vjf_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, float_index * 4, 0, 0);"):
+        "own: vjf_ld4_plain -- used for L^-1 of a launch WITHOUT an RLS update only (mg_varN): written once at the start of the launch, "
         "read for the first time behind the MG_C_XT count (no earlier copy in this CU's L1: a launch starts with it invalidated)",
     ("vjf_mega_moments.h", "else { m = S[P.off[VJF_SLOT_PRIOR_MEAN] + c]; l = S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c]; }"): "const: the prior (the posterior is an sc1 load)",
     ("vjf_mega_moments.h", "if (b < nb) ep = eps_s[(size_t)(b0 + b) * dz + c];"): "const: the noise input",
     ("vjf_mega_moments.h", "} else if (b < nb) v = u_t[(size_t)(b0 + b) * du + c - dz];"): "const: the control input",
     ("vjf_mega_sgd.h", "const int4 pi = *reinterpret_cast<const int4*>(A.sl_pidx + (size_t)quad * 4);"): "const: slab tables",
     ("vjf_mega_sgd.h", "const int4 ci = *reinterpret_cast<const int4*>(A.sl_cidx + (size_t)quad * 4);"): "const: slab tables",
-    ("vjf_mega_sgd.h", "if (pi.x >= 0 && ci.x >= 0) mg_st(img + ci.x, th[pi.x]);"): "const: the parameters of a launch that does not update them",
-    ("vjf_mega_sgd.h", "if (pi.y >= 0 && ci.y >= 0) mg_st(img + ci.y, th[pi.y]);"): "const: as above",
-    ("vjf_mega_sgd.h", "if (pi.z >= 0 && ci.z >= 0) mg_st(img + ci.z, th[pi.z]);"): "const: as above",
-    ("vjf_mega_sgd.h", "if (pi.w >= 0 && ci.w >= 0) mg_st(img + ci.w, th[pi.w]);"): "const: as above",
+    ("vjf_mega_sgd.h", "if (pi.x >= 0 && ci.x >= 0) vjf_st_wt(img + ci.x, th[pi.x]);"): "const: the parameters of a launch that does not update them",
+    ("vjf_mega_sgd.h", "if (pi.y >= 0 && ci.y >= 0) vjf_st_wt(img + ci.y, th[pi.y]);"): "const: as above",
+    ("vjf_mega_sgd.h", "if (pi.z >= 0 && ci.z >= 0) vjf_st_wt(img + ci.z, th[pi.z]);"): "const: as above",
+    ("vjf_mega_sgd.h", "if (pi.w >= 0 && ci.w >= 0) vjf_st_wt(img + ci.w, th[pi.w]);"): "const: as above",
     # ---- SGD role
     ("vjf_mega_sgd.h", "const float lr_dec = SC[VJF_SC_LR_DEC], lr_rec = SC[VJF_SC_LR_REC];"): "const: set by the host between launches",
     ("vjf_mega_sgd.h", "pi = *reinterpret_cast<const int4*>(A.sl_pidx + (size_t)quad * 4);"): "const: slab tables",
@@ -68,8 +68,8 @@ ALLOW = {
     ("vjf_post_kernel.h", "s_x[r * LX + c] = (r < n && c < dz) ? Wold[(size_t)r * dz + c] : 0.f;"): "acq: the failed-factorisation path acquires before it reads the state",
     ("vjf_post_kernel.h", "const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);"):
         "const: the forgetting factor, set by the host between launches (and behind the same path's acquire)",
-    ("vjf_post_kernel.h", "for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));"): "acq: same path",
-    ("vjf_post_kernel.h", "vjf_store_wt(A.xt + (size_t)j * n + k, Wc[e]);"): "const: w_chol as the launch found it (the launch's first act)",
+    ("vjf_post_kernel.h", "for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_st_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));"): "acq: same path",
+    ("vjf_post_kernel.h", "vjf_st_wt(A.xt + (size_t)j * n + k, Wc[e]);"): "const: w_chol as the launch found it (the launch's first act)",
     # ---- vjf_chol_kernel.h (vjf_chol_body is shared with the per-step kernels)
     ("vjf_chol_kernel.h", "float sig = S[P.off[VJF_SLOT_TR_LOGVAR]];"): "const: the value the launch found; from the second step on it is replaced by the hand-off word's",
     ("vjf_chol_kernel.h", "const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);"):

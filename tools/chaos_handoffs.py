@@ -1,6 +1,6 @@
 """Diagnostic and regression check of the hand-offs between roles: sequences on the routes whose workgroups or kernels run BESIDE each
 other (the one-launch route; the three-stream per-step route) under the diagnostic build, in which one workgroup in eight is held for
-up to 200 us in front of a wait or a signal (-DVJF_CHAOS, vjf_plan.h), against the one-stream per-step kernels, which have no hand-offs.
+up to 200 us in front of a wait or a signal (-DVJF_CHAOS, vjf_handoff.h), against the one-stream per-step kernels, which have no hand-offs.
 An access that is ordered only by the usual timing of the roles -- not by a count -- shows as a wrong result within a few sequences
 (round 2: the Gram role's double buffer, which a late RLS role read one step too late; 21 to 40 of 40 sequences deviated at
 configs[1]'s shape with the Cholesky or the operand workgroups held, one fresh process in fifty without any hold).

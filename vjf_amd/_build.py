@@ -40,7 +40,7 @@ def is_stale(lib=None):
 
 def build(force=False, verbose=False, chaos=False):
     """Compile csrc/*.hip into libvjf_hip.so if missing or older than its sources.  chaos=True: the diagnostic build
-    libvjf_hip_chaos.so (-DVJF_CHAOS, see vjf_plan.h) instead."""
+    libvjf_hip_chaos.so (-DVJF_CHAOS, see vjf_handoff.h) instead."""
     lib = CHAOS_LIB if chaos else LIB
     if not force and not is_stale(lib):
         return lib

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# VJF_LIB=chaos loads the diagnostic build of the same sources (-DVJF_CHAOS, vjf_plan.h: workgroups are held at random in front of
+# VJF_LIB=chaos loads the diagnostic build of the same sources (-DVJF_CHAOS, vjf_handoff.h: workgroups are held at random in front of
 # their hand-offs; tools/chaos_handoffs.py) -- same ABI, same kernels otherwise
 #  (any other VJF_LIB=name: libvjf_hip_name.so, a hand-built experiment of the same sources)
 _variant = os.environ.get("VJF_LIB", "")

@@ -18,6 +18,7 @@
 #include "../../include/vjf_hip.h"
 #include "vjf_chol_kernel.h"
 #include "vjf_gram_kernel.h"
+#include "vjf_handoff.h"
 #include "vjf_mega_kernel.h"
 #include "vjf_ops_kernels.h"
 #include "vjf_plan.h"
@@ -33,7 +34,7 @@
 #include "vjf_host_routes.h"
 
 #ifdef VJF_CHAOS
-// diagnostic build: which workgroups are held, and where (vjf_plan.h), from the environment at every entry
+// diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
 static void chaos_refresh(const vjf_ctx* c) {
     const int range[6] = {getenv("VJF_CHAOS_LO") ? atoi(getenv("VJF_CHAOS_LO")) : 0, getenv("VJF_CHAOS_HI") ? atoi(getenv("VJF_CHAOS_HI")) : 1 << 30,
                           getenv("VJF_CHAOS_SITE") ? atoi(getenv("VJF_CHAOS_SITE")) : -1, getenv("VJF_CHAOS_KIND") ? atoi(getenv("VJF_CHAOS_KIND")) : 0,

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_gram_kernel.h"   // vjf_f32x16
+#include "vjf_handoff.h"
 #include "vjf_plan.h"
 
 #define VJF_CHOL_THREADS 512
@@ -119,8 +120,8 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
     if (A.replay_pass) return;                                 // (the scalars were settled by the first pass)
     if (tid == 0) {                                            // ---- scalars: loss, likelihood log-variance
         if (A.replay_mask) {
-            __hip_atomic_store(A.replay_rho, S[P.off[VJF_SLOT_LIK_LOGVAR]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(A.replay_mask, replay ? ((ok_r ? 0u : 1u) | (ok_d ? 0u : 2u) | (ok_h ? 0u : 4u)) : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            vjf_st_wt(A.replay_rho, S[P.off[VJF_SLOT_LIK_LOGVAR]]);
+            vjf_st_wt(A.replay_mask, replay ? ((ok_r ? 0u : 1u) | (ok_d ? 0u : 2u) | (ok_h ? 0u : 4u)) : 0u);
         }
         if (!ok_r) l_recon = 0.f;
         if (!ok_d) l_dyn = 0.f;
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
         }
         if (A.run_word) {
             bool there = false;
-            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
+            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {      // (its own loop, not vjf_poll_count: two words, both there at the same look)
                 const unsigned r = __hip_atomic_load(A.run_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const unsigned q = __hip_atomic_load(A.start_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((int)(r - A.run_epoch) >= 0 && (int)(q - A.start_target) >= 0) { there = true; break; }
@@ -182,11 +183,7 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
     float* S = A.state;
     if (A.wait_count) {
         if (tid == 0) {
-            bool there = false;
-            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-                if ((int)(__hip_atomic_load(A.wait_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - A.wait_target) >= 0) { there = true; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
+            const bool there = vjf_poll_count<4>(A.wait_count, A.wait_target, nullptr);
             if (!there) vjf_status_or(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_OPERAND);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
                 float4 o;
                 o.x = fmaf(g[q].x, inv_v, p[q].x); o.y = fmaf(g[q].y, inv_v, p[q].y); o.z = fmaf(g[q].z, inv_v, p[q].z); o.w = fmaf(g[q].w, inv_v, p[q].w);
                 float* dstp = Pm + (size_t)(i0 + row) * n + c4;
-                if (A.done_count) { vjf_store_wt(dstp, o.x); vjf_store_wt(dstp + 1, o.y); vjf_store_wt(dstp + 2, o.z); vjf_store_wt(dstp + 3, o.w); }
+                if (A.done_count) { vjf_st_wt(dstp, o.x); vjf_st_wt(dstp + 1, o.y); vjf_st_wt(dstp + 2, o.z); vjf_st_wt(dstp + 3, o.w); }
                 else *reinterpret_cast<float4*>(dstp) = o;
             }
         }
@@ -254,7 +251,7 @@ __global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A
         if (c < dz && i0 + r < n) {
             const float v = ((s_r[r * 17 + c] + s_r[(16 + r) * 17 + c]) + s_r[(32 + r) * 17 + c]) + s_r[(48 + r) * 17 + c];
             const float gv = v + FDX[(size_t)(i0 + r) * dz + c] * inv_v;
-            if (A.done_count) vjf_store_wt(A.gbuf + (size_t)(i0 + r) * dz + c, gv); else A.gbuf[(size_t)(i0 + r) * dz + c] = gv;
+            if (A.done_count) vjf_st_wt(A.gbuf + (size_t)(i0 + r) * dz + c, gv); else A.gbuf[(size_t)(i0 + r) * dz + c] = gv;
         }
     }
     if (A.done_count) vjf_wg_signal_wt(A.done_count, tid);
@@ -728,7 +725,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     // gate on this word, so that they do not sit on 15 CUs before there is anything for them to do
     // (self_prep: the word is stored once this step's operands are in registers -- the operand kernel, which overwrites the
     //  state's P, starts behind a gate on it)
-    if (A.post && !A.self_prep && tid == 0) __hip_atomic_store(A.flags_out + VJF_CHOL_MAXBLK + 2, it_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (A.post && !A.self_prep && tid == 0) vjf_st_wt(A.flags_out + VJF_CHOL_MAXBLK + 2, it_epoch);
     float* s_blk = lds;                               // ntri blocks: lower block triangle of P -> L -> L^-1
     float* s_aux = s_blk + (size_t)ntri * 1024;       // nbl blocks: inverted diagonal blocks of L; later scratch
     float* s_g = s_aux + (size_t)nbl * 1024;          // npad x DZP  g, later W
@@ -791,7 +788,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         auto sigma_wait = [&]() {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // operands in registers: the state's P may now be overwritten
             __syncthreads();
-            if (tid == 0) __hip_atomic_store(A.flags_out + VJF_CHOL_MAXBLK + 2, it_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) vjf_st_wt(A.flags_out + VJF_CHOL_MAXBLK + 2, it_epoch);
             vjf_chaos(tid, A.wait_count, 1);
             if (A.sig_word && it_wait_target != 0u) {
                 // sigma inside the hand-off word: one poll, no second load; the exit count of the post workgroups is checked by the
@@ -799,7 +796,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 if (tid == 0) {
                     bool there = false;
                     unsigned bits = 0u;
-                    for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
+                    for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {          // (its own loop, not vjf_poll_count: 64 bits, the payload rides in the word)
                         const unsigned long long v = __hip_atomic_load(A.sig_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((unsigned)(v >> 32) == it_epoch - 1u) { there = true; bits = (unsigned)v; break; }
                         if ((spins & 255u) == 255u && vjf_abort_seen(SC + VJF_SC_STATUS)) break;
@@ -817,14 +814,10 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             if (!vjf_wg_wait_sc1(A.wait_count, it_wait_target, tid, SC + VJF_SC_STATUS, (A.flags & VJF_FLAG_HANDOFF_ACQUIRE) != 0u)) { vjf_status_or(SC + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_SIGMA); *s_dead = 1; }
             sig = __hip_atomic_load(S + P.off[VJF_SLOT_TR_LOGVAR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         };
-        typedef unsigned chol_u4 __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t r_G = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t r_G = vjf_rsrc(G);
         auto g4 = [&](int gi, int gj) {                                 // 4 entries of G, zero outside the matrix
             if (!(gi < n && gj < n)) return make_float4(0.f, 0.f, 0.f, 0.f);
-            if (A.stat_count) {                                         // (another role's stores of this launch: sc1, past this CU's L1)
-                const chol_u4 v4 = __builtin_amdgcn_raw_buffer_load_b128(r_G, (gi * n + gj) * 4, 0, 16);
-                return make_float4(__uint_as_float(v4[0]), __uint_as_float(v4[1]), __uint_as_float(v4[2]), __uint_as_float(v4[3]));
-            }
+            if (A.stat_count) return vjf_ld4_sc1(r_G, gi * n + gj);       // (another role's stores of this launch: sc1, past this CU's L1)
             return *reinterpret_cast<const float4*>(G + (size_t)gi * n + gj);
         };
         constexpr int NT = VJF_CHOL_THREADS - 64, NQ = ((VJF_CHOL_MAXBLK * (VJF_CHOL_MAXBLK + 1) / 2 - 1) * 256 + NT - 1) / NT;
@@ -896,8 +889,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         };
         // post mode: one finished 32x32 block out to global memory (one wavefront, 4 float4 per lane)
         // Write-through (sc1) 16-byte stores: the bytes are in memory, visible to every XCD, once the storing wavefront's vmcnt
-        // has drained -- no release fence (cdna guide, Guideline 16 R1).  The asm store is not counted by the compiler: the
-        // publishing code below drains it by hand.
+        // has drained -- no release fence (cdna guide, Guideline 16 R1); the publishing code below drains them by hand (vjf_st4_wt).
         auto put_block = [&](const float* blk, float* dst, int ld, int gi0, int gj0, bool lower_only) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -907,16 +899,13 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 o[1] = (!lower_only || c4 + 1 <= r) ? blk[vsw(r, c4 + 1)] : 0.f;
                 o[2] = (!lower_only || c4 + 2 <= r) ? blk[vsw(r, c4 + 2)] : 0.f;
                 o[3] = (!lower_only || c4 + 3 <= r) ? blk[vsw(r, c4 + 3)] : 0.f;
-                if (gi0 + r < ld && gj0 + c4 < ld) {
-                    float* p = dst + (size_t)(gi0 + r) * ld + gj0 + c4;
-                    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(o) : "memory");
-                }
+                if (gi0 + r < ld && gj0 + c4 < ld) vjf_st4_wt(dst + (size_t)(gi0 + r) * ld + gj0 + c4, o);
             }
         };
         auto publish = [&](int k0, int k1, unsigned fail) {             // one wavefront: its stores drained, then the flags
             vjf_chaos(lane, A.flags_out + k0, 2);                       // (diagnostic builds: the wavefront is held)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane >= k0 && lane < k1) __hip_atomic_store(A.flags_out + lane, (it_epoch << 1) | fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane >= k0 && lane < k1) vjf_st_wt(A.flags_out + lane, (it_epoch << 1) | fail);
         };
         // ---- The column loop without a workgroup barrier in it.  The dependent chain -- Dinv_k from the factor chain of block (k,k),
         //      the one panel tile L_{k+1,k} = A_{k+1,k} Dinv_k^T, the last update of block (k+1,k+1), the next chain -- runs on
@@ -1015,7 +1004,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                     if (!v_ok[0]) break;
                     if (k == 0 && lscr_guard) {                         // (this wavefront alone writes the scratch copies)
                         bool there = false;
-                        for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
+                        for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {      // (its own loop, not vjf_poll_count: as a call it moves code in the pair and one-launch kernels)
                             if ((int)(__hip_atomic_load(A.wait_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - it_wait_target) >= 0) { there = true; break; }
                             if ((spins & 255u) == 255u && vjf_abort_seen(SC + VJF_SC_STATUS)) break;
                             __builtin_amdgcn_s_sleep(1);

@@ -86,7 +86,7 @@ constexpr size_t kMaxLds = 160 * 1024;
 //    of the previous one, whatever context and stream that came from.  While a device has a single context with the route the
 //    stream's own order does this and no event is used; the second context's creation synchronises the device once and switches
 //    the chain on for good.
-//  * a page of pinned host memory through which a launch that has given up a wait tells the host (vjf_plan.h, vjf_status_or).
+//  * a page of pinned host memory through which a launch that has given up a wait tells the host (VJF_MIRROR_SLOT, vjf_plan.h; the waits themselves: vjf_handoff.h).
 struct DevShared {
     std::mutex mu;
     int mega_ctxs = 0;          // live contexts whose plan the one-launch route serves

@@ -1,8 +1,10 @@
 // vjf_mega_common.h -- what the roles of the one-launch route (vjf_mega_kernel.h) share: the counter block and the launch's
-// arguments, the LDS and slab layouts, sc1 loads / write-through stores, the MFMA product routines, the grid's first and last act.
+// arguments, the LDS and slab layouts, the MFMA product routines, the grid's first and last act (waits, sc1 loads and write-through
+// stores: vjf_handoff.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_chol_kernel.h"
+#include "vjf_handoff.h"
 #include "vjf_plan.h"
 #include "vjf_post_kernel.h"
 #include "vjf_trial_mfma_kernel.h"   // vjf_f32x4
@@ -67,7 +69,7 @@ __device__ __forceinline__ bool mg_grid_resident(unsigned* cnt, float* status, i
     if (threadIdx.x == 0) {
         __hip_atomic_fetch_add(cnt + MG_C_ALIVE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         bool there = false;
-        for (unsigned spins = 0; spins < (1u << 17); ++spins) {
+        for (unsigned spins = 0; spins < (1u << 17); ++spins) {        // (its own loop, not vjf_poll_count: the short bound above and a plain >=)
             if (__hip_atomic_load(cnt + MG_C_ALIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= gridDim.x + (unsigned)extra) { there = true; break; }
             if ((spins & 255u) == 255u && vjf_abort_seen(status)) break;
             __builtin_amdgcn_s_sleep(VJF_POLL_SLEEP);
@@ -216,24 +218,6 @@ static inline size_t vjf_mega_prep_lds_floats(const VjfPlan& P) {
     return (size_t)16 * VJF_PREPG_LDP(P.n) + (size_t)P.n * 17 + (size_t)VJF_MG_WAVES * 16 * 17 + 16 * 17 + 64;
 }
 
-__device__ __forceinline__ float mg_ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mg_st(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// 16-byte sc1 loads (buffer_load_dwordx4 ... sc1): what another workgroup stored write-through, read past this CU's vector L1.
-// The descriptor's base must be workgroup-uniform (it lives in scalar registers); the per-lane part is the 32-bit float index.
-typedef unsigned mg_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mg_rsrc(const float* uniform_base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uniform_base), 0, 0x7fffffff, 0x00020000);
-}
-// the same as a PLAIN load (through this CU's L1): only for bytes that are constants of the launch by the time they are first read
-__device__ __forceinline__ float4 mg_ld4_plain(__amdgpu_buffer_rsrc_t r, int float_index) {
-    const mg_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, float_index * 4, 0, 0);
-    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-}
-__device__ __forceinline__ float4 mg_ld4(__amdgpu_buffer_rsrc_t r, int float_index) {
-    const mg_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, float_index * 4, 0, 16);               // aux 16 = sc1
-    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-}
-
 // (mg_tanh, the Tanh kernels' tanh: vjf_act.h)
 
 // acc_g(row = 4*(lane>>4)+r, col = lane&15) += sum_{kb <= k < ke} Ag[k*lda + m0 + row] * Xs[k*LD + 16 g + col]   (g = 0, 1)
@@ -249,7 +233,7 @@ __device__ __forceinline__ void mg_mma2_ld16(float (&a)[16], const float* __rest
     const unsigned row = rv ? (unsigned)(m0 + i) : 0u;
     const int klast = ke - 1;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) { const int k = min(kb + 4 * (s0 + q) + kk, klast); a[q] = mg_ld(Ag + row + (unsigned)k * (unsigned)lda); }
+    for (int q = 0; q < 16; ++q) { const int k = min(kb + 4 * (s0 + q) + kk, klast); a[q] = vjf_ld_sc1(Ag + row + (unsigned)k * (unsigned)lda); }
     // (rows beyond M are masked where the value is USED: a select on a load's destination right behind the load makes the compiler
     //  wait for the load there, and the batch would no longer be in flight beside the previous batch's MFMAs)
 }
@@ -288,7 +272,7 @@ __device__ __forceinline__ void mg_mma2(vjf_f32x4& acc0, vjf_f32x4& acc1, const 
     //  resident kernels and take vjf_mega_lite_act_kernel's scratch from 100 to 104 bytes -- profiles/mega_split_isa.txt, candidate 3)
     auto ld16 = [&](float (&a)[16], int s0) {          // steps s0 .. s0 + 15: clamped rows, masked at use
 #pragma unroll
-        for (int q = 0; q < 16; ++q) { const int k = min(kb + 4 * (s0 + q) + kk, klast); a[q] = mg_ld(Ag + row + (unsigned)k * ulda); }
+        for (int q = 0; q < 16; ++q) { const int k = min(kb + 4 * (s0 + q) + kk, klast); a[q] = vjf_ld_sc1(Ag + row + (unsigned)k * ulda); }
     };
     auto mm16 = [&](const float (&a)[16], int s0) {
 #pragma unroll
@@ -360,7 +344,7 @@ __device__ __forceinline__ void mg_var2(float& v2a, float& v2b, __amdgpu_buffer_
         const bool inB = sb >= SA;                                            // (uniform)
         const int t0 = 4 * (inB ? sb - SA : sb), off = inB ? offB : offA;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const int kq = 16 * (t0 + q) + 4 * kk; a[q] = mg_ld4(rx, off + (kq + 3 < n ? 16 * (t0 + q) : 0)); }
+        for (int q = 0; q < 4; ++q) { const int kq = 16 * (t0 + q) + 4 * kk; a[q] = vjf_ld4_sc1(rx, off + (kq + 3 < n ? 16 * (t0 + q) : 0)); }
     };
     auto mmb = [&](const float4 (&a)[4], int sb) {
         const bool inB = sb >= SA;
@@ -448,12 +432,6 @@ __device__ __forceinline__ void mg_mma2_lds(vjf_f32x4& acc0, vjf_f32x4& acc1, co
     }
 }
 
-// 16-byte write-through store (the asm store is not counted by the compiler: every hand-off drains vmcnt by hand before it signals)
-__device__ __forceinline__ void mg_st4(float* p, float x, float y, float z, float w) {
-    vjf_f32x4 o = {x, y, z, w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(o) : "memory");
-}
-
 // e / d for e d < 2^32 without the ~30-instruction integer division: one v_mul_hi_u32 with m = ceil(2^32 / d) (d >= 2)
 __device__ __forceinline__ unsigned mg_magic(unsigned d) { return d < 2 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); }
 __device__ __forceinline__ int mg_div(int e, unsigned m) { return m ? (int)__umulhi((unsigned)e, m) : e; }
@@ -465,9 +443,9 @@ __device__ __forceinline__ int mg_div(int e, unsigned m) { return m ? (int)__umu
 // Which workgroups share an XCD is a placement guess (blockIdx round-robin); a wrong guess costs speed, never correctness.
 __device__ __forceinline__ void mg_warm(const float* base, int nfloats, int wg, int tid) {
     const int nq = nfloats >> 2, per = (nq + 15) >> 4, q0 = ((wg >> 3) & 15) * per;
-    const __amdgpu_buffer_rsrc_t rb = mg_rsrc(base);
+    const __amdgpu_buffer_rsrc_t rb = vjf_rsrc(base);
     for (int q = q0 + tid; q < min(nq, q0 + per); q += VJF_MG_THREADS) {
-        const float4 v = mg_ld4(rb, q * 4);
+        const float4 v = vjf_ld4_sc1(rb, q * 4);
         asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
     }
 }
@@ -476,12 +454,12 @@ __device__ __forceinline__ void mg_warm(const float* base, int nfloats, int wg, 
 // its own loads and retires these behind them
 __device__ __forceinline__ void mg_warm_issue(const float* base, int nfloats, int wg, int tid, float4 (&r)[2]) {
     const int nq = nfloats >> 2, per = (nq + 15) >> 4, q0 = ((wg >> 3) & 15) * per, q1 = min(nq, q0 + per);
-    const __amdgpu_buffer_rsrc_t rb = mg_rsrc(base);
+    const __amdgpu_buffer_rsrc_t rb = vjf_rsrc(base);
     r[0] = r[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q0 + tid < q1) r[0] = mg_ld4(rb, (q0 + tid) * 4);
-    if (q0 + tid + VJF_MG_THREADS < q1) r[1] = mg_ld4(rb, (q0 + tid + VJF_MG_THREADS) * 4);
+    if (q0 + tid < q1) r[0] = vjf_ld4_sc1(rb, (q0 + tid) * 4);
+    if (q0 + tid + VJF_MG_THREADS < q1) r[1] = vjf_ld4_sc1(rb, (q0 + tid + VJF_MG_THREADS) * 4);
     for (int q = q0 + tid + 2 * VJF_MG_THREADS; q < q1; q += VJF_MG_THREADS) {
-        const float4 v = mg_ld4(rb, q * 4);
+        const float4 v = vjf_ld4_sc1(rb, q * 4);
         asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
     }
 }
@@ -552,8 +530,8 @@ __device__ __forceinline__ void mg_grad_tile(const float* D, int M, int m0, cons
     const int mq = m0 + 4 * (lane >> 4), j = j0 + (lane & 15);      // (rows m >= M of D are the zero row: the padding columns get 0)
     if (j < rows && mq < ldm) {
         float* p = blk + (size_t)j * ldm + mq;
-        if (!first) { acc[0] += mg_ld(p); acc[1] += mg_ld(p + 1); acc[2] += mg_ld(p + 2); acc[3] += mg_ld(p + 3); }   // (a later tile of the workgroup)
-        mg_st4(p, acc[0], acc[1], acc[2], acc[3]);
+        if (!first) { acc[0] += vjf_ld_sc1(p); acc[1] += vjf_ld_sc1(p + 1); acc[2] += vjf_ld_sc1(p + 2); acc[3] += vjf_ld_sc1(p + 3); }   // (a later tile of the workgroup)
+        vjf_st4_wt(p, acc[0], acc[1], acc[2], acc[3]);
     }
 }
 
@@ -568,7 +546,7 @@ __device__ __forceinline__ void mg_sum_losses(const VjfMegaArgs& A, int t, float
         const int sc = tid >> 5, l = tid & 31, slot = sc < RS_SDX2 ? sc : RS_RESID;
         double d = 0.0;
         if (sc < RS_SDX2 || want_resid)
-            for (int w = l; w < A.n_trial; w += 32) d += (double)mg_ld(A.slab_late + (size_t)w * A.late_len + A.slab_len + ring + slot);
+            for (int w = l; w < A.n_trial; w += 32) d += (double)vjf_ld_sc1(A.slab_late + (size_t)w * A.late_len + A.slab_len + ring + slot);
         d = vjf_sum32(d);
         // (the residual leaves as the mean square: its sum over 32768 x 16 elements has more digits than a float keeps)
         if (l == 0) s_sc[slot] = slot == RS_RESID ? (float)(d / ((double)Bf * (double)dz)) : (float)d;
@@ -608,7 +586,7 @@ __device__ __forceinline__ void mg_varN(float (&v2)[NG], __amdgpu_buffer_rsrc_t 
         const bool inB = sb >= SA;
         const int t0 = 4 * (inB ? sb - SA : sb), off = inB ? offB : offA;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const int kq = 16 * (t0 + q) + 4 * kk; a[q] = mg_ld4_plain(rx, off + (kq + 3 < n ? 16 * (t0 + q) : 0)); }   // (plain: L^-1 of a launch without an RLS update is written once, before its first read)
+        for (int q = 0; q < 4; ++q) { const int kq = 16 * (t0 + q) + 4 * kk; a[q] = vjf_ld4_plain(rx, off + (kq + 3 < n ? 16 * (t0 + q) : 0)); }   // (plain: L^-1 of a launch without an RLS update is written once, before its first read)
     };
     auto mmb = [&](const float4 (&a)[4], int sb) {
         const bool inB = sb >= SA;

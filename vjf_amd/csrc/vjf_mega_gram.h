@@ -31,7 +31,7 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
     __syncthreads();
     const int r0 = hg * A.gram_rows, r1 = min(A.B, r0 + A.gram_rows);
     float* myslab = A.gslab + (size_t)hg * ntri * 1024;
-    const __amdgpu_buffer_rsrc_t r_gslab = mg_rsrc(A.gslab);
+    const __amdgpu_buffer_rsrc_t r_gslab = vjf_rsrc(A.gslab);
     const int c = lane & 31, kh = lane >> 5;
     for (int e = 0; e < A.T; ++e) {
         float* red = (e & 1) ? A.red1 : A.red0;
@@ -62,8 +62,8 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
                 float v = 0.f;
                 if (b < r1) {
                     if (c2 < dz) {
-                        const float m = mu_s ? mg_ld(mu_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_MEAN] + c2];   // (sc1: no acquire
-                        const float l = mu_s ? mg_ld(lv_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c2]; //  behind the waits)
+                        const float m = mu_s ? vjf_ld_sc1(mu_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_MEAN] + c2];   // (sc1: no acquire
+                        const float l = mu_s ? vjf_ld_sc1(lv_s + (size_t)b * dz + c2) : S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c2]; //  behind the waits)
                         v = fmaf(eps_s[(size_t)b * dz + c2], expf(0.5f * l), m);
                     } else {
                         v = u_e[(size_t)b * du + c2 - dz];
@@ -130,7 +130,7 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
                     if (c0 + VJF_MG_GROWS >= r1) {
                         float* sl = myslab + (size_t)tt * 1024;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) mg_st4(sl + (j * 64 + lane) * 4, acc[q][4 * j], acc[q][4 * j + 1], acc[q][4 * j + 2], acc[q][4 * j + 3]);
+                        for (int j = 0; j < 4; ++j) vjf_st4_wt(sl + (j * 64 + lane) * 4, acc[q][4 * j], acc[q][4 * j + 1], acc[q][4 * j + 2], acc[q][4 * j + 3]);
                     }
                 }
             }
@@ -142,7 +142,7 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
                 if (tt < ntri) {
                     float* sl = myslab + (size_t)tt * 1024;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) mg_st4(sl + (j * 64 + lane) * 4, 0.f, 0.f, 0.f, 0.f);
+                    for (int j = 0; j < 4; ++j) vjf_st4_wt(sl + (j * 64 + lane) * 4, 0.f, 0.f, 0.f, 0.f);
                 }
             }
         }
@@ -170,7 +170,7 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
             auto load16 = [&](float4 (&tq)[16], int quad, int h0) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q)
-                    tq[q] = (quad < nq && h0 + q < h1) ? mg_ld4(r_gslab, quad * 4 + (h0 + q) * ntri * 1024) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    tq[q] = (quad < nq && h0 + q < h1) ? vjf_ld4_sc1(r_gslab, quad * 4 + (h0 + q) * ntri * 1024) : make_float4(0.f, 0.f, 0.f, 0.f);
             };
             auto add16 = [&](float4& v, const float4 (&tq)[16]) {
 #pragma unroll
@@ -201,15 +201,15 @@ __device__ __forceinline__ void vjf_mega_gram(const VjfPlan& P, const VjfMegaArg
                     const int gc = (code & 255) * 32 + (ln & 31);
                     const int gr0 = (code >> 8) * 32 + 8 * j + 4 * (ln >> 5);            // the quad: rows gr0 .. gr0 + 3 of column gc
                     if (gr0 + 3 < n && gc < n) {
-                        mg_st4(red + P.red_G + (size_t)gc * n + gr0, vv[0], vv[1], vv[2], vv[3]);                // row gc, columns gr0 .. gr0 + 3
-                        mg_st4(red + P.red_G + (size_t)(gr0 + a4) * n + (gc - a4), o[0], o[1], o[2], o[3]);        // row gr0 + a4, columns gc - a4 .. + 3
+                        vjf_st4_wt(red + P.red_G + (size_t)gc * n + gr0, vv[0], vv[1], vv[2], vv[3]);                // row gc, columns gr0 .. gr0 + 3
+                        vjf_st4_wt(red + P.red_G + (size_t)(gr0 + a4) * n + (gc - a4), o[0], o[1], o[2], o[3]);        // row gr0 + a4, columns gc - a4 .. + 3
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int gr = gr0 + r;
                             if (gr < n && gc < n && ((code >> 8) != (code & 255) || gc <= gr)) {
-                                mg_st(red + P.red_G + (size_t)gr * n + gc, vv[r]);
-                                mg_st(red + P.red_G + (size_t)gc * n + gr, vv[r]);
+                                vjf_st_wt(red + P.red_G + (size_t)gr * n + gc, vv[r]);
+                                vjf_st_wt(red + P.red_G + (size_t)gc * n + gr, vv[r]);
                             }
                         }
                     }

@@ -18,7 +18,7 @@
 //
 // Hand-offs are monotone workgroup counters in memory: producer = write-through stores, every storing wavefront drains vmcnt, the
 // workgroup barrier, one relaxed agent-scope add; consumer = one lane polls about once a microsecond (bounded; VJF_POLL_SLEEP,
-// vjf_plan.h), the workgroup barrier, and every handed-off byte is read with an sc1 load (MI355X guide, "sc1 loads in place of the
+// vjf_handoff.h), the workgroup barrier, and every handed-off byte is read with an sc1 load (MI355X guide, "sc1 loads in place of the
 // acquire"; VJF_HANDOFF_ACQUIRE=1 adds an agent-scope acquire behind every wait).  Nothing ever waits for work of a launch that has not been submitted: every
 // producer is a workgroup of this grid, and the grid is resident as a whole.  All sums are taken in a fixed order: results do not
 // depend on timing, and a sequence cut into chunks gives the same bits as one piece.

@@ -56,7 +56,7 @@ __device__ __forceinline__ bool mg_moments_pass(const VjfPlan& P, const VjfMegaA
         float v = 0.f;
         if (c < dz) {
             float m, l, ep = 0.f;
-            if (mu_s) { m = b < nb ? mg_ld(mu_s + (size_t)(b0 + b) * dz + c) : 0.f; l = b < nb ? mg_ld(lv_s + (size_t)(b0 + b) * dz + c) : 0.f; }
+            if (mu_s) { m = b < nb ? vjf_ld_sc1(mu_s + (size_t)(b0 + b) * dz + c) : 0.f; l = b < nb ? vjf_ld_sc1(lv_s + (size_t)(b0 + b) * dz + c) : 0.f; }
             else { m = S[P.off[VJF_SLOT_PRIOR_MEAN] + c]; l = S[P.off[VJF_SLOT_PRIOR_LOGVAR] + c]; }
             if (b < nb) ep = eps_s[(size_t)(b0 + b) * dz + c];
             v = fmaf(ep, expf(0.5f * l), m);
@@ -99,7 +99,7 @@ __device__ __forceinline__ bool mg_moments_pass(const VjfPlan& P, const VjfMegaA
     VJF_MG_STAMP(13);
     int mean_nsl = 1;
     {   // predictive variance and mean: vjf_mega_trial's stage 2, wavefront for wavefront
-        const __amdgpu_buffer_rsrc_t r_xt = mg_rsrc(A.xt);
+        const __amdgpu_buffer_rsrc_t r_xt = vjf_rsrc(A.xt);
         const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
         const int ntile = (n + 15) >> 4;
         float v2[NG];
@@ -160,14 +160,14 @@ __device__ __forceinline__ bool mg_moments_pass(const VjfPlan& P, const VjfMegaA
         float* mb = A.mom + ((size_t)(col < TR ? tile0 : tile1) * 2 + (size_t)(t & 1)) * (size_t)mlen;
         float v = 0.f;
         for (int sl = 0; sl < mean_nsl; ++sl) v += s_part[(size_t)(sl * 16 + j) * LD + col];
-        mg_st(mb + j * TR + b, s_xu[j * LD + col] + v);
-        mg_st(mb + TR * dz + j * TR + b, v);
+        vjf_st_wt(mb + j * TR + b, s_xu[j * LD + col] + v);
+        vjf_st_wt(mb + TR * dz + j * TR + b, v);
     }
     if (tid < ncol) {
         float* mb = A.mom + ((size_t)(tid < TR ? tile0 : tile1) * 2 + (size_t)(t & 1)) * (size_t)mlen;
         float v = 0.f;
         for (int w = 0; w < NW; ++w) v += s_red[w * NC + tid];
-        mg_st(mb + 2 * TR * dz + (tid & 31), logf(v));
+        vjf_st_wt(mb + 2 * TR * dz + (tid & 31), logf(v));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -191,7 +191,7 @@ __device__ __forceinline__ void vjf_mega_moments(const VjfPlan& P, const VjfMega
         vjf_status_or(SCW + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_K1);
     if (vjf_abort_wg()) return;
     // (w_chol upper triangular: the state's flag, or what the trial workgroups saw while they transposed it)
-    const bool tri = mg_ld(SCW + VJF_SC_TRI_CLEAN) != 0.f || __hip_atomic_load(A.cnt + MG_C_XT + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
+    const bool tri = vjf_ld_sc1(SCW + VJF_SC_TRI_CLEAN) != 0.f || __hip_atomic_load(A.cnt + MG_C_XT + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
     for (int t = 0; t < A.T; ++t) {
         // this workgroup's tiles mw, mw + n_mom, ..: two at a time side by side (every operand load of L^-1 serves both), a last one alone
         // (ONE instantiation of the pass, four column groups, for both cases -- tile1 < 0: the second half idles.  With a two-group

@@ -17,7 +17,7 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
     const unsigned npost = (unsigned)(A.n_rls - 1);
     const unsigned* runw = A.cnt + MG_C_COLFLAGS + VJF_CHOL_MAXBLK + 2;
     // (every byte taken from other roles is read with sc1 loads behind the counts' polls and the workgroup barrier: no acquires)
-    const __amdgpu_buffer_rsrc_t r_early = mg_rsrc(A.slab_early);
+    const __amdgpu_buffer_rsrc_t r_early = vjf_rsrc(A.slab_early);
     for (int t = 0; t < A.T; ++t) {
         float* red = (t & 1) ? A.red1 : A.red0;
         // (four counts, ONE acquire: behind the last of them)
@@ -44,7 +44,7 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
                     float4 tq[16];
 #pragma unroll
                     for (int q = 0; q < 16; ++q)
-                        tq[q] = (w0 + q < w1) ? mg_ld4(r_early, src + (w0 + q) * A.early_len) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        tq[q] = (w0 + q < w1) ? vjf_ld4_sc1(r_early, src + (w0 + q) * A.early_len) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                     for (int q = 0; q < 16; ++q) { v.x += tq[q].x; v.y += tq[q].y; v.z += tq[q].z; v.w += tq[q].w; }
                 }
@@ -60,23 +60,23 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     s_f[(r4 + q) * 17 + c] = vv[q];
-                    if (i0 + r4 + q < n && c < dz) mg_st(red + P.red_FDX + (size_t)(i0 + r4 + q) * dz + c, vv[q]);
+                    if (i0 + r4 + q < n && c < dz) vjf_st_wt(red + P.red_FDX + (size_t)(i0 + r4 + q) * dz + c, vv[q]);
                 }
             }
             if (pw == 0 && tid < 64) {                                             // sum |dx|^2: one wavefront, strided partial sums, xor tree
                 float q2 = 0.f;
-                for (int w = tid; w < A.n_trial; w += 64) q2 += mg_ld(base + (size_t)w * A.early_len + (size_t)16 * ldn + RS_SDX2);
+                for (int w = tid; w < A.n_trial; w += 64) q2 += vjf_ld_sc1(base + (size_t)w * A.early_len + (size_t)16 * ldn + RS_SDX2);
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) q2 += __shfl_xor(q2, o, 64);
-                if (tid == 0) mg_st(red + P.red_SC + RS_SDX2, q2);
+                if (tid == 0) vjf_st_wt(red + P.red_SC + RS_SDX2, q2);
             }
         }
-        const float inv_v = expf(-mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]));
-        const float lam = vjf_shrink_of(mg_ld(SCW + VJF_SC_SHRINK));
+        const float inv_v = expf(-vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]));
+        const float lam = vjf_shrink_of(vjf_ld_sc1(SCW + VJF_SC_SHRINK));
         float* Pm = S + P.off[VJF_SLOT_W_PREC];
         const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
         const float* G = red + P.red_G;
-        const __amdgpu_buffer_rsrc_t r_P = mg_rsrc(Pm), r_G = mg_rsrc(G);
+        const __amdgpu_buffer_rsrc_t r_P = vjf_rsrc(Pm), r_G = vjf_rsrc(G);
         const int n4 = n >> 2;
         const unsigned m_n4 = mg_magic(n4);
         for (int e0 = tid; e0 < 16 * n4; e0 += 4 * NT) {
@@ -86,8 +86,8 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
                 const int e = e0 + q * NT, row = mg_div(e, m_n4), c4 = (e - row * n4) * 4;
                 const bool in = e < 16 * n4 && i0 + row < n;
                 const size_t off = in ? (size_t)(i0 + row) * n + c4 : 0;
-                p[q] = mg_ld4(r_P, (int)off);                                  // (P: this workgroup's own rows -- and the y / W loop's after a failed factorisation)
-                g[q] = mg_ld4(r_G, (int)off);
+                p[q] = vjf_ld4_sc1(r_P, (int)off);                                  // (P: this workgroup's own rows -- and the y / W loop's after a failed factorisation)
+                g[q] = vjf_ld4_sc1(r_G, (int)off);
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {                                      // lambda P: what the update adds to, and the P of g = (lambda P) W
@@ -101,13 +101,13 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
                 const bool in = i0 + row < n;
                 float* d = s_p + row * ldp + c4;
                 d[0] = in ? p[q].x : 0.f; d[1] = in ? p[q].y : 0.f; d[2] = in ? p[q].z : 0.f; d[3] = in ? p[q].w : 0.f;
-                if (in) mg_st4(Pm + (size_t)(i0 + row) * n + c4, fmaf(g[q].x, inv_v, p[q].x), fmaf(g[q].y, inv_v, p[q].y),
+                if (in) vjf_st4_wt(Pm + (size_t)(i0 + row) * n + c4, fmaf(g[q].x, inv_v, p[q].x), fmaf(g[q].y, inv_v, p[q].y),
                                fmaf(g[q].z, inv_v, p[q].z), fmaf(g[q].w, inv_v, p[q].w));
             }
         }
         for (int e = tid; e < n * 16; e += NT) {
             const int k = e >> 4, cc = e & 15;
-            s_w[k * 17 + cc] = cc < dz ? mg_ld(Wm + (size_t)k * dz + cc) : 0.f;
+            s_w[k * 17 + cc] = cc < dz ? vjf_ld_sc1(Wm + (size_t)k * dz + cc) : 0.f;
         }
         __syncthreads();
         {
@@ -128,7 +128,7 @@ __device__ __forceinline__ void vjf_mega_prep(const VjfPlan& P, const VjfMegaArg
                 float v = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) v += s_r[(w * 16 + r) * 17 + cc];
-                mg_st(A.gbuf + (size_t)(i0 + r) * dz + cc, v + s_f[r * 17 + cc] * inv_v);
+                vjf_st_wt(A.gbuf + (size_t)(i0 + r) * dz + cc, v + s_f[r * 17 + cc] * inv_v);
             }
         }
         vjf_wg_signal_wt(A.cnt + MG_C_PREP, tid);

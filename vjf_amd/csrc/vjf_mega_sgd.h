@@ -28,7 +28,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
     const int w1 = min(A.n_trial, (part + 1) * npq);
     // Every byte this role takes from the trial role (late slabs, loss sums) is read with sc1 loads behind the count's poll and the
     // workgroup barrier: no agent-scope acquire (vjf_wg_wait_sc1)
-    const __amdgpu_buffer_rsrc_t r_late = mg_rsrc(A.slab_late);
+    const __amdgpu_buffer_rsrc_t r_late = vjf_rsrc(A.slab_late);
     // A lane group serves the same quads in every step: the table entries and the parameters of its first round stay in
     // registers for the whole launch (a longer parameter vector reads the later rounds' from memory each step)
     const int q00 = (sw * NT) >> 3;
@@ -43,10 +43,10 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
             ci = *reinterpret_cast<const int4*>(A.sl_cidx + (size_t)quad * 4);
             grp = A.sl_grp[quad];
             const float* th = S + P.train_off;
-            if (pi.x >= 0) w[0] = mg_ld(th + pi.x);                                // (this lane's own stores of the step before)
-            if (pi.y >= 0) w[1] = mg_ld(th + pi.y);
-            if (pi.z >= 0) w[2] = mg_ld(th + pi.z);
-            if (pi.w >= 0) w[3] = mg_ld(th + pi.w);
+            if (pi.x >= 0) w[0] = vjf_ld_sc1(th + pi.x);                                // (this lane's own stores of the step before)
+            if (pi.y >= 0) w[1] = vjf_ld_sc1(th + pi.y);
+            if (pi.z >= 0) w[2] = vjf_ld_sc1(th + pi.z);
+            if (pi.w >= 0) w[3] = vjf_ld_sc1(th + pi.w);
         }
     };
     fetch(q00 + (tid >> 3), k_pi, k_ci, k_grp, k_w);
@@ -55,10 +55,10 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
         // stores the parameters of its quads; the trial role waits for all of them before its first step
         auto put = [&](const int4& pi, const int4& ci, const float (&w)[4]) {
             float* img = const_cast<float*>(A.img);
-            if (pi.x >= 0 && ci.x >= 0) mg_st(img + ci.x, w[0]);
-            if (pi.y >= 0 && ci.y >= 0) mg_st(img + ci.y, w[1]);
-            if (pi.z >= 0 && ci.z >= 0) mg_st(img + ci.z, w[2]);
-            if (pi.w >= 0 && ci.w >= 0) mg_st(img + ci.w, w[3]);
+            if (pi.x >= 0 && ci.x >= 0) vjf_st_wt(img + ci.x, w[0]);
+            if (pi.y >= 0 && ci.y >= 0) vjf_st_wt(img + ci.y, w[1]);
+            if (pi.z >= 0 && ci.z >= 0) vjf_st_wt(img + ci.z, w[2]);
+            if (pi.w >= 0 && ci.w >= 0) vjf_st_wt(img + ci.w, w[3]);
         };
         put(k_pi, k_ci, k_w);
         for (int q0 = q00 + qstride; q0 < nquad; q0 += qstride) {
@@ -75,8 +75,8 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
     // memory round trips, 2-4 us, on the path of every gated step: the gate waits for this workgroup too)
     float k_rho = 0.f, k_nlik = 0.f, k_sig = 0.f, k_ntr = 0.f;
     if (sw == 0 && tid == 0) {
-        k_rho = mg_ld(S + P.off[VJF_SLOT_LIK_LOGVAR]); k_nlik = mg_ld(SC + VJF_SC_N_LIK);
-        if (do_upd && warm) { k_sig = mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]); k_ntr = mg_ld(SC + VJF_SC_N_TR); }
+        k_rho = vjf_ld_sc1(S + P.off[VJF_SLOT_LIK_LOGVAR]); k_nlik = vjf_ld_sc1(SC + VJF_SC_N_LIK);
+        if (do_upd && warm) { k_sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]); k_ntr = vjf_ld_sc1(SC + VJF_SC_N_TR); }
     }
     for (int t = 0; t < A.T; ++t) {
       float l_recon = 0.f, l_dyn = 0.f, ent = 0.f;
@@ -113,14 +113,14 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
             const int src = (act ? quad : 0) * 4;                                  // (float index into the late slabs)
 #pragma unroll
             for (int q = 0; q < 16; ++q)
-                tq[q] = (act && part * npq + q < w1) ? mg_ld4(r_late, src + (part * npq + q) * A.late_len) : make_float4(0.f, 0.f, 0.f, 0.f);
+                tq[q] = (act && part * npq + q < w1) ? vjf_ld4_sc1(r_late, src + (part * npq + q) * A.late_len) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (!have_sums) take_sums();
             for (int wq = part * npq + 16; wq < w1; wq += 16) {                   // (more than 128 trial workgroups: further rounds)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) { v.x += tq[q].x; v.y += tq[q].y; v.z += tq[q].z; v.w += tq[q].w; }
 #pragma unroll
                 for (int q = 0; q < 16; ++q)
-                    tq[q] = (act && wq + q < w1) ? mg_ld4(r_late, src + (wq + q) * A.late_len) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    tq[q] = (act && wq + q < w1) ? vjf_ld4_sc1(r_late, src + (wq + q) * A.late_len) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) { v.x += tq[q].x; v.y += tq[q].y; v.z += tq[q].z; v.w += tq[q].w; }
@@ -142,7 +142,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
                 // has kept in registers, still have to reach the blob when this is the last step of the launch
                 if (tl && q0 == q00 && t == A.T - 1) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) if (pidx[r] >= 0) mg_st(S + P.train_off + pidx[r], wold[r]);
+                    for (int r = 0; r < 4; ++r) if (pidx[r] >= 0) vjf_st_wt(S + P.train_off + pidx[r], wold[r]);
                 }
                 return;
             }
@@ -153,8 +153,8 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
                 g = fminf(fmaxf(g, -1.f), 1.f);                                // clip_grad_value_ (model.py:210)
                 const float wn = wold[r] - (grp == 1 ? lr_dec : lr_rec) * g;
                 wold[r] = wn;
-                if (wst) mg_st(S + P.train_off + pidx[r], wn);
-                if (cidx[r] >= 0) mg_st(cdst + cidx[r], wn);
+                if (wst) vjf_st_wt(S + P.train_off + pidx[r], wn);
+                if (cidx[r] >= 0) vjf_st_wt(cdst + cidx[r], wn);
             }
         };
         if (!do_sgd) take_sums();
@@ -166,7 +166,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
             round(q0, pi, ci, grp, w);
             if (q0 == q00) { k_w[0] = w[0]; k_w[1] = w[1]; k_w[2] = w[2]; k_w[3] = w[3]; }
         }
-        if (pass == 0 && t == 0 && mode_rls && mg_ld(SC + VJF_SC_TRI_CLEAN) == 0.f) {
+        if (pass == 0 && t == 0 && mode_rls && vjf_ld_sc1(SC + VJF_SC_TRI_CLEAN) == 0.f) {
             // one-time clearing of the halves the inverse loops never write (block-lower part of w_chol, block-upper part of
             // w_pchol): every reader of the dense w_chol of step 0 has signalled its late slab
             float* Wc = S + P.off[VJF_SLOT_W_CHOL];
@@ -174,8 +174,8 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
             const int n = P.n;
             for (int e = sw * NT + tid; e < n * n; e += n_live * NT) {
                 const int i = e / n, j = e - i * n;
-                if ((i >> 5) < (j >> 5)) mg_st(Lm + e, 0.f);
-                if ((i >> 5) > (j >> 5)) { mg_st(Wc + e, 0.f); mg_st(const_cast<float*>(A.xt) + (size_t)j * n + i, 0.f); }   // (and its row-major transpose)
+                if ((i >> 5) < (j >> 5)) vjf_st_wt(Lm + e, 0.f);
+                if ((i >> 5) > (j >> 5)) { vjf_st_wt(Wc + e, 0.f); vjf_st_wt(const_cast<float*>(A.xt) + (size_t)j * n + i, 0.f); }   // (and its row-major transpose)
             }
         }
         const unsigned bad = (ok_r ? 0u : 1u) | (ok_d ? 0u : 2u) | (ok_h ? 0u : 4u);
@@ -204,10 +204,10 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
                     const float acc = fminf(k_nlik, 1000.f), tot = acc + Bf;
                     rho = logf((acc / tot) * expf(rho) + (Bf / tot) * mse);
                     k_nlik = tot;
-                    mg_st(SC + VJF_SC_N_LIK, tot);
+                    vjf_st_wt(SC + VJF_SC_N_LIK, tot);
                 }
                 k_rho = rho;
-                if (do_sgd || do_upd) mg_st(S + P.off[VJF_SLOT_LIK_LOGVAR], rho);
+                if (do_sgd || do_upd) vjf_st_wt(S + P.off[VJF_SLOT_LIK_LOGVAR], rho);
             }
             if (do_upd && warm) {
                 // warm-up: no RLS update, the state-noise running variance from the residual with the launch's W (model.py:370-377)
@@ -215,8 +215,8 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
                 const float acc = fminf(k_ntr, 500.f), tot = acc + Bf;                            // running_var, size_cap=500 (model.py:375)
                 k_sig = logf((acc / tot) * expf(k_sig) + (Bf / tot) * mse);
                 k_ntr = tot;
-                mg_st(S + P.off[VJF_SLOT_TR_LOGVAR], k_sig);
-                mg_st(SC + VJF_SC_N_TR, tot);
+                vjf_st_wt(S + P.off[VJF_SLOT_TR_LOGVAR], k_sig);
+                vjf_st_wt(SC + VJF_SC_N_TR, tot);
             }
         }
         __syncthreads();
@@ -228,12 +228,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
     // (the launch's last act on the triangle flag: set once every SGD workgroup has cleared its share -- they all have signalled
     //  step 0 by then; the kernel boundary makes it visible to the next launch)
     if (sw == 0 && tid == 0 && mode_rls && SC[VJF_SC_TRI_CLEAN] == 0.f) {
-        bool there = false;
-        for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-            if ((int)(__hip_atomic_load(A.cnt + MG_C_SGD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)n_live) >= 0) { there = true; break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (there) mg_st(SC + VJF_SC_TRI_CLEAN, 1.f);
+        if (vjf_poll_count<2>(A.cnt + MG_C_SGD, (unsigned)n_live, nullptr)) vjf_st_wt(SC + VJF_SC_TRI_CLEAN, 1.f);
     }
 }
 
@@ -252,10 +247,10 @@ __device__ __forceinline__ void mg_build_image(const VjfPlan& P, const VjfMegaAr
         if (quad < nquad && part == 0) {
             const int4 pi = *reinterpret_cast<const int4*>(A.sl_pidx + (size_t)quad * 4);
             const int4 ci = *reinterpret_cast<const int4*>(A.sl_cidx + (size_t)quad * 4);
-            if (pi.x >= 0 && ci.x >= 0) mg_st(img + ci.x, th[pi.x]);
-            if (pi.y >= 0 && ci.y >= 0) mg_st(img + ci.y, th[pi.y]);
-            if (pi.z >= 0 && ci.z >= 0) mg_st(img + ci.z, th[pi.z]);
-            if (pi.w >= 0 && ci.w >= 0) mg_st(img + ci.w, th[pi.w]);
+            if (pi.x >= 0 && ci.x >= 0) vjf_st_wt(img + ci.x, th[pi.x]);
+            if (pi.y >= 0 && ci.y >= 0) vjf_st_wt(img + ci.y, th[pi.y]);
+            if (pi.z >= 0 && ci.z >= 0) vjf_st_wt(img + ci.z, th[pi.z]);
+            if (pi.w >= 0 && ci.w >= 0) vjf_st_wt(img + ci.w, th[pi.w]);
         }
     }
     vjf_wg_signal_wt(A.cnt + MG_C_IMG, tid);

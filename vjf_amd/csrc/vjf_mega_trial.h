@@ -106,12 +106,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             if (t > 0) {
                 vjf_chaos(tid, cnt + MG_C_SGD, 1);
                 if (tid == 0) {
-                    bool there = false;
-                    for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-                        if ((int)(__hip_atomic_load(cnt + MG_C_SGD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)t * (unsigned)(RLS ? A.n_sgd : A.n_sgd_live)) >= 0) { there = true; break; }
-                        if ((spins & 255u) == 255u && vjf_abort_seen(SCW + VJF_SC_STATUS)) break;
-                        __builtin_amdgcn_s_sleep(RLS ? VJF_POLL_SLEEP : VJF_POLL_SLEEP_LITE);
-                    }
+                    const bool there = vjf_poll_count<RLS ? VJF_POLL_SLEEP : VJF_POLL_SLEEP_LITE>(cnt + MG_C_SGD, (unsigned)t * (unsigned)(RLS ? A.n_sgd : A.n_sgd_live), SCW + VJF_SC_STATUS);
                     const bool rls = !rls_in && (int)(__hip_atomic_load(cnt + MG_C_PDONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)t * npost) >= 0;
                     const unsigned mw = __hip_atomic_load(cnt + MG_C_MASK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (!tl || (A.flags & VJF_FLAG_HANDOFF_ACQUIRE)) {         // (parameters read from the state with plain loads; or the conservative hand-off)
@@ -214,10 +209,10 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                     if (tid == 0) {
                         bool there = false;
                         unsigned v = 0u;
-                        for (unsigned spins = 0; spins < (1u << 21); ++spins) {
+                        for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {       // (its own loop, not vjf_poll_count: the count it saw is kept, ring_seen)
                             v = __hip_atomic_load(cnt + MG_C_SGD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if ((int)(v - need) >= 0) { there = true; break; }
-                            if ((spins & 255u) == 255u && ((unsigned)__hip_atomic_load(SCW + VJF_SC_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & VJF_STATUS_WAIT_MASK)) break;
+                            if ((spins & 255u) == 255u && vjf_abort_seen(SCW + VJF_SC_STATUS)) break;
                             __builtin_amdgcn_s_sleep(RLS ? VJF_POLL_SLEEP : VJF_POLL_SLEEP_LITE);
                         }
                         if (!there) vjf_status_or(SCW + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_GATE);
@@ -239,8 +234,8 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                     if (rls_in) mg_warm(A.xt, P.n * P.n, wg, tid);
                 }
                 if (rls_in) {
-                    sig = mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]);
-                    tri = tri_launch || mg_ld(SCW + VJF_SC_TRI_CLEAN) != 0.f;  // w_chol known upper triangular
+                    sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);
+                    tri = tri_launch || vjf_ld_sc1(SCW + VJF_SC_TRI_CLEAN) != 0.f;  // w_chol known upper triangular
                 }
                 if (t == 0) {                                                 // (the row-major copy of L^-1 of this launch: the inverse loops' first act)
                     if (!mode_rls) {
@@ -256,7 +251,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                             const int k = e / n, j = e - k * n;
                             const float v = Wc[e];
                             below = below || (k > j && v != 0.f);
-                            mg_st(xtw + (size_t)j * n + k, v);
+                            vjf_st_wt(xtw + (size_t)j * n + k, v);
                         }
                         if (__syncthreads_or(below ? 1 : 0) && tid == 0) __hip_atomic_fetch_add(cnt + MG_C_XT + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         vjf_wg_signal_wt(cnt + MG_C_XT, tid);
@@ -275,7 +270,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             auto moments_a = [&]() {
             // ---- stage 2: predictive variance sum_j (Phi w_chol)_j^2 (module.py:75-76) and pt.mean = xs + Phi W (module.py:77)
             if (!replay) {
-                const __amdgpu_buffer_rsrc_t r_xt = mg_rsrc(A.xt);
+                const __amdgpu_buffer_rsrc_t r_xt = vjf_rsrc(A.xt);
                 const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
                 const int ntile = (n + 15) >> 4;
                 float v2a = 0.f, v2b = 0.f;
@@ -356,12 +351,12 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             }
             float4 wv[2];
             const bool warm_now = first && !replay && rls_now && !rls_in;      // the RLS update landed while this workgroup waited for the parameters
-            if (first && !replay) rho = mg_ld(S + P.off[VJF_SLOT_LIK_LOGVAR]);  // (the SGD role's)
-            if (first && !replay && !mode_rls) sig = mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]);   // (warm-up: the SGD role's too; else a constant)
+            if (first && !replay) rho = vjf_ld_sc1(S + P.off[VJF_SLOT_LIK_LOGVAR]);  // (the SGD role's)
+            if (first && !replay && !mode_rls) sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);   // (warm-up: the SGD role's too; else a constant)
             if (warm_now) {
                 mg_warm_issue(A.xt, P.n * P.n, wg, tid, wv);
-                sig = mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]);
-                tri = mg_ld(SCW + VJF_SC_TRI_CLEAN) != 0.f;
+                sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);
+                tri = vjf_ld_sc1(SCW + VJF_SC_TRI_CLEAN) != 0.f;
                 rls_in = true;
             }
             if (first && tl && !replay && t == 0) {                            // (the image of this launch: the SGD role's first act)
@@ -373,13 +368,13 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                                                                                //  that updates nothing: they are the launch's constants, staged once)
                 // the parameters of this step into LDS: the image the SGD role keeps has the layout of the region, so this is a flat
                 // 16-byte copy with all of a thread's loads in flight -- one round trip
-                const __amdgpu_buffer_rsrc_t r_img = mg_rsrc(A.img);
+                const __amdgpu_buffer_rsrc_t r_img = vjf_rsrc(A.img);
                 float4* dst = reinterpret_cast<float4*>(smem + Lo.th0);
                 const int n4 = Lo.th_len >> 2;
                 for (int q0 = tid; q0 < n4; q0 += 8 * NT) {
                     float4 v[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) if (q0 + q * NT < n4) v[q] = mg_ld4(r_img, (q0 + q * NT) * 4);
+                    for (int q = 0; q < 8; ++q) if (q0 + q * NT < n4) v[q] = vjf_ld4_sc1(r_img, (q0 + q * NT) * 4);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) if (q0 + q * NT < n4) dst[q0 + q * NT] = v[q];
                 }
@@ -481,13 +476,13 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                         const int e = 4 * e4 + c, b = mg_div(e, m_dz), j = e - b * dz;
                         vm[c] = s_mu[j * LD + b]; vl[c] = s_lv[j * LD + b];
                     }
-                    mg_st4(mrow + 4 * e4, vm[0], vm[1], vm[2], vm[3]);
-                    mg_st4(lrow + 4 * e4, vl[0], vl[1], vl[2], vl[3]);
+                    vjf_st4_wt(mrow + 4 * e4, vm[0], vm[1], vm[2], vm[3]);
+                    vjf_st4_wt(lrow + 4 * e4, vl[0], vl[1], vl[2], vl[3]);
                 }
                 for (int e = 4 * n4 + tid; e < ne; e += NT) {
                     const int b = mg_div(e, m_dz), j = e - b * dz;
-                    mg_st(mrow + e, s_mu[j * LD + b]);
-                    mg_st(lrow + e, s_lv[j * LD + b]);
+                    vjf_st_wt(mrow + e, s_mu[j * LD + b]);
+                    vjf_st_wt(lrow + e, s_lv[j * LD + b]);
                 }
                 // (the moments role's tag for this posterior goes out behind the decoder, below: its stores are acknowledged by then, and
                 //  a drain here was 1.5 us on the path of every step; the moments role is a step ahead)
@@ -540,8 +535,8 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                     const int fq = m0 + 4 * (lane >> 4), col = lane & 15;
                     if (col < dz && fq < ldn) {
                         float* p = early + (size_t)col * ldn + fq;
-                        if (!first) { acc[0] += mg_ld(p); acc[1] += mg_ld(p + 1); acc[2] += mg_ld(p + 2); acc[3] += mg_ld(p + 3); }
-                        mg_st4(p, acc[0], acc[1], acc[2], acc[3]);
+                        if (!first) { acc[0] += vjf_ld_sc1(p); acc[1] += vjf_ld_sc1(p + 1); acc[2] += vjf_ld_sc1(p + 2); acc[3] += vjf_ld_sc1(p + 3); }
+                        vjf_st4_wt(p, acc[0], acc[1], acc[2], acc[3]);
                     }
                 }
             }
@@ -572,7 +567,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 float v = 0.f;
                 for (int bb = 0; bb < TR; ++bb) v += s_sc[bb * RS_N + RS_SDX2];
                 s_wg[RS_SDX2] += v;
-                if (last) mg_st(early + (size_t)16 * ldn + RS_SDX2, s_wg[RS_SDX2]);
+                if (last) vjf_st_wt(early + (size_t)16 * ldn + RS_SDX2, s_wg[RS_SDX2]);
             }
             if (first) VJF_MG_STAMP(26);
             // One tile per workgroup and the RLS update of the previous step still to be taken in, but there by now (config B: it
@@ -594,8 +589,8 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 if (vjf_abort_wg()) return;
                 // (sigma and the triangle flag first, then this workgroup's share of the L2 warm-up with its loads left in flight: the
                 //  variance tiles' own operand loads go out behind them instead of waiting a round trip for them)
-                sig = mg_ld(S + P.off[VJF_SLOT_TR_LOGVAR]);
-                tri = mg_ld(SCW + VJF_SC_TRI_CLEAN) != 0.f;
+                sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);
+                tri = vjf_ld_sc1(SCW + VJF_SC_TRI_CLEAN) != 0.f;
                 if (fuse_fwd) {
                     // every wavefront's stores of the forward pass (posterior, early slab) and these two loads are behind it: the count
                     // the operand and Gram roles wait for
@@ -616,7 +611,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 const float* mb = A.mom + ((size_t)tile * 2 + (size_t)(tc & 1)) * (size_t)((2 * dz + 1) * TR);
                 for (int e = tid; e < TR * (2 * dz + 1); e += NT) {
                     const int j = e >> 5, b = e & 31;
-                    const float v = mg_ld(mb + e);
+                    const float v = vjf_ld_sc1(mb + e);
                     if (j < dz) s_pm[j * LD + b] = v;
                     else if (j < 2 * dz) { if (want_resid) s_dmu[(j - dz) * LD + b] = v; }
                     else s_plv[b] = v;
@@ -846,7 +841,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             if (last) {
                 // the workgroup's late slab is complete: loss sums, then the signal the SGD role waits for
                 __syncthreads(); MG_PHASE();
-                if ((tid < RS_SDX2 || (tid == RS_RESID && want_resid)) && !replay) mg_st(late + A.slab_len + 8 * (tc % VJF_MG_RING) + tid, s_wg[tid]);
+                if ((tid < RS_SDX2 || (tid == RS_RESID && want_resid)) && !replay) vjf_st_wt(late + A.slab_len + 8 * (tc % VJF_MG_RING) + tid, s_wg[tid]);
                 if (gated) vjf_wg_signal_wt(cnt + (replay ? MG_C_REDO_B : MG_C_BWD), tid);
                 else {
                     // No gate between the steps of this launch (nothing changes between them): the trial workgroups are not in step

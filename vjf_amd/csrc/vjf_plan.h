@@ -169,129 +169,12 @@ struct VjfJob {
     int tw, tb;        // kind 1: rows of the plan's trainable-tensor table that the weight / the bias belong to (tb -1: none)
 };
 
-// Bound of every wait of one kernel for another (polls; ~2 us each with the sleep between them, VJF_POLL_SLEEP: ~4 s).  Long enough for a
-// host that is late with its launches, or a peer rank that is late with its half of a collective; short enough that a sequence
-// that really is stuck (a launch held behind a resident kernel's hardware queue) is given up quickly.
-#define VJF_WAIT_SPINS (1u << 21)
-// s_sleep argument (units of 64 cycles) between two polls of a hand-off word in memory.  The polls of a launch -- 256 workgroups, most
-// of them waiting most of the time -- all go to the few memory-side lines of the counter block, and they delay each other AND the
-// write-through traffic of the step: with back-to-back polls (1) config B ran 56.3 us a step, with 12: 55.1, 24: 53.4-53.8,
-// 40: 52.3-52.8, 64: 53.2 (same box, two runs each; a poll every ~1 us costs less in detection latency than the contention of
-// faster ones; four out-of-phase pollers per workgroup: 60.4).  Spreading the counters over 4-KB pages of their own changed nothing.
-// (Config C, whose trial role takes its operands from L2, would like 64 better: 74.8 against 76.5 us a step; config B 53.2 against 52.5.)
-#ifndef VJF_POLL_SLEEP_LITE
-#define VJF_POLL_SLEEP_LITE 16
-#endif
-#ifndef VJF_POLL_SLEEP
-#define VJF_POLL_SLEEP 40
-#endif
 #ifdef __HIPCC__
-// Hand-offs between kernels that run beside each other on different streams (no kernel boundary between producer and
-// consumer).  Producer, whole workgroup: every storing wavefront drains its stores, the workgroup barrier, one lane releases
-// at agent scope (L2 write-back), drains again, then the relaxed agent-scope count.  Consumer, whole workgroup: one lane
-// polls (relaxed, bounded), acquires at agent scope, its vmcnt drained, the workgroup barrier, and only then the plain loads
-// (MI355X guide, visibility across XCDs, valid forms).
-// -DVJF_CHAOS (diagnostic builds only, tools/chaos_handoffs.sh): one workgroup in eight is held for up to 200 us in front of a wait or
-// a signal, so that an access which is ordered by the usual timing of the roles and not by a hand-off shows as a wrong result.
-#ifdef VJF_CHAOS
-__device__ int vjf_chaos_range[6] = {0, 1 << 30, -1, 0, 20000, 7};          // workgroups [lo, hi) are held (VJF_CHAOS_LO / _HI) at count word [2] (-1: any; VJF_CHAOS_SITE), kind [3] (0 any, 1 waits, 2 signals),
-                                                                            // for up to [4] ticks of 10 ns (VJF_CHAOS_TICKS), one time in [5] + 1 (a mask; VJF_CHAOS_MASK)
-__device__ const unsigned* vjf_chaos_base = nullptr;
-#endif
-__device__ __forceinline__ void vjf_chaos(int tid, const unsigned* count, int kind) {
-#ifdef VJF_CHAOS
-    if (tid == 0 && (int)blockIdx.x >= vjf_chaos_range[0] && (int)blockIdx.x < vjf_chaos_range[1] &&
-        (vjf_chaos_range[2] < 0 || count - vjf_chaos_base == vjf_chaos_range[2]) && (vjf_chaos_range[3] == 0 || vjf_chaos_range[3] == kind)) {
-        const unsigned long long t0 = wall_clock64();                       // 100 MHz
-        unsigned h = ((unsigned)t0 * 2654435761u) ^ (blockIdx.x * 40503u);
-        h ^= h >> 13; h *= 0x5bd1e995u; h ^= h >> 15;
-        const unsigned d = (h & (unsigned)vjf_chaos_range[5]) == 0u ? (h >> 8) % (unsigned)vjf_chaos_range[4] : 0u;
-        while (wall_clock64() - t0 < d) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
-}
-__device__ __forceinline__ void vjf_wg_signal(unsigned* count, int tid) {
-    vjf_chaos(tid, count, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-// A wait that ran out somewhere in the sequence (status detail bits 0x1ff00, include/vjf_hip.h) ends every other wait at once:
-// the sequence is lost anyway (the host re-runs it), and nothing should sit through its own bound step after step.
-__device__ __forceinline__ bool vjf_abort_seen(const float* status) {
-    if (!status) return false;
-    const float f = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return ((unsigned)f & VJF_STATUS_WAIT_MASK) != 0u;
-}
-// The same verdict for a whole workgroup: the lane that polled in the wait just before (vjf_wg_wait / vjf_wg_wait_sc1, given a status
-// word) read the status word once more behind its poll and left what it saw in this LDS word in front of the wait's barrier --
-// every thread of the workgroup takes the SAME decision to leave (a thread-by-thread read could split a workgroup around its later
-// barriers when the bits are raised between two threads' loads).  4 bytes of static LDS in the kernels that wait.
-__shared__ int vjf_s_abort_word;
-__device__ __forceinline__ bool vjf_abort_wg() { return vjf_s_abort_word != 0; }
-// The same for a workgroup whose outputs went out as write-through stores (in memory once vmcnt has drained): no L2 write-back
-// (an agent-scope release by every workgroup of a kernel that runs beside the trial kernel costs that kernel microseconds).
-__device__ __forceinline__ void vjf_wg_signal_wt(unsigned* count, int tid) {
-    vjf_chaos(tid, count, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The wait without the acquire: for consumers that read EVERY handed-off byte with sc1 loads (which bypass this CU's vector L1;
-// the producer stored write-through and drained before it signalled) -- MI355X guide, "sc1 loads in place of the acquire".  One
-// lane polls, the workgroup barrier, then the sc1 loads.
-// `fence` = true adds the acquire (VJF_HANDOFF_ACQUIRE=1; the default of the one-launch route is the sc1 loads alone).
-#define VJF_FLAG_HANDOFF_ACQUIRE 0x40000000u      /* internal flag bit of the kernels' `flags` words */
-// (SLEEP: the pause between two polls, in units of 64 cycles -- the training launch has ~250 workgroups polling one 1-KB block and
-//  wants them a microsecond apart, VJF_POLL_SLEEP; the launches without an RLS update have a third of the pollers and take 16)
-template <int SLEEP = VJF_POLL_SLEEP>
-__device__ __forceinline__ bool vjf_wg_wait_sc1(const unsigned* count, unsigned target, int tid, const float* status = nullptr, bool fence = false) {
-    bool there = true;
-    vjf_chaos(tid, count, 1);
-    if (tid == 0) {
-        there = false;
-        for (unsigned spins = 0; spins < (1u << 21); ++spins) {
-            if ((int)(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) { there = true; break; }
-            if ((spins & 255u) == 255u && status && ((unsigned)__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & VJF_STATUS_WAIT_MASK)) break;
-            __builtin_amdgcn_s_sleep(SLEEP);
-        }
-        if (fence) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        vjf_s_abort_word = (!there || vjf_abort_seen(status)) ? 1 : 0;
-    }
-    __syncthreads();
-    return there;
-}
 // The forgetting factor of the RLS update as the scalar slot holds it: 0 (a state from before the slot had a meaning) is 1.
 __device__ __forceinline__ float vjf_shrink_of(float stored) { return stored == 0.f ? 1.0f : stored; }
 // lambda p, rounded on its own: the sums and fmaf it feeds keep the form (and, at lambda = 1, the bits) they had without it --
 // the empty statement keeps the compiler from contracting the product into them
 __device__ __forceinline__ float vjf_lam_mul(float p, float lam) { float r = p * lam; asm("" : "+v"(r)); return r; }
-__device__ __forceinline__ void vjf_store_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// returns false (lane 0 only; the others get true) when the count did not arrive within the bound
-__device__ __forceinline__ bool vjf_wg_wait(const unsigned* count, unsigned target, int tid, const float* status = nullptr) {
-    bool there = true;
-    vjf_chaos(tid, count, 1);
-    if (tid == 0) {
-        there = false;
-        for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-            if ((int)(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) { there = true; break; }
-            if ((spins & 255u) == 255u && vjf_abort_seen(status)) break;
-            __builtin_amdgcn_s_sleep(VJF_POLL_SLEEP);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        vjf_s_abort_word = (!there || vjf_abort_seen(status)) ? 1 : 0;
-    }
-    __syncthreads();
-    return there;
-}
-#endif
-
-#ifdef __HIPCC__
 // sum over the 32 lanes of a half wavefront, fixed xor tree (the loss sums: every kernel that forms them uses this order)
 __device__ __forceinline__ double vjf_sum32(double v) {
 #pragma unroll
@@ -308,14 +191,3 @@ __device__ __forceinline__ double vjf_sum32(double v) {
 // incorrect register class.  V_CMP_NE_U32_e32 0, $src_shared_base" -- whatever form the store took.]
 #define VJF_MIRROR_WORDS 256
 #define VJF_MIRROR_SLOT(status_ptr) ((unsigned)(((uintptr_t)(status_ptr)) >> 4) & (VJF_MIRROR_WORDS - 1))
-// OR status bits into the status scalar (a float holding a small integer).  Kernels of one step may run on two
-// streams (vjf_filter_seq), so the read-modify-write is a compare-and-swap loop.
-__device__ __forceinline__ void vjf_status_or(float* p, unsigned bits) {
-    unsigned* u = reinterpret_cast<unsigned*>(p);
-    unsigned old = *u, assumed;
-    do {
-        assumed = old;
-        const float nv = (float)((unsigned)__uint_as_float(assumed) | bits);
-        old = atomicCAS(u, assumed, __float_as_uint(nv));
-    } while (old != assumed);
-}

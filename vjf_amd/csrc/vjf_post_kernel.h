@@ -12,12 +12,11 @@
 //       (model.py:375-377).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vjf_handoff.h"
 #include "vjf_plan.h"
 #include "vjf_chol_kernel.h"         // VJF_CHOL_MAXBLK, vjf_f32x16
 #include "vjf_trial_mfma_kernel.h"   // vjf_f32x4
 
-// bound of every in-kernel wait (each poll is an L2 round trip + s_sleep: ~0.5 s in all); time-out -> status bit, never a hang
-#define VJF_SPIN_LIMIT VJF_WAIT_SPINS
 #define VJF_POST_THREADS 512
 #define VJF_POST_KPAR 4                // wavefronts = 2 row tiles x 4 interleaved block sums
 #define VJF_POST_LDB 33               // padded leading dimension of a 32x32 block in LDS
@@ -103,28 +102,13 @@ __device__ __forceinline__ void post_mma32(vjf_f32x4& acc, const float* Bs, int 
 // sc1 loads -- 16-byte buffer loads or 4-byte agent-scope loads, which bypass this CU's vector L1 -- behind the poll that matched
 // and the workgroup barrier: no agent-scope acquire (an L1 invalidate the whole workgroup would wait ~1.7 us for) per column
 // (MI355X guide, "sc1 loads in place of the acquire").  The rare failure path, which reads more, does acquire.
-typedef unsigned post_u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t post_rsrc(const float* base, size_t nfloats) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)(nfloats * 4), 0x00020000);
-}
-__device__ __forceinline__ float4 post_ld4(__amdgpu_buffer_rsrc_t r, size_t float_off) {
-    const post_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(float_off * 4), 0, 16);      // aux 16 = sc1
-    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-}
-__device__ __forceinline__ float post_ld(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Wait (one lane polls, relaxed, bounded) until the Cholesky kernel has published flag word `k` for this epoch; the workgroup
 // barrier; then the sc1 loads of the column (see above).  Returns 0 = there, 1 = the factorisation failed, 2 = timed out.
 __device__ __forceinline__ int post_wait_column(const unsigned* flags, unsigned epoch, int k, int* s_ctl, int tid, const float* status, bool fence = false) {
     vjf_chaos(tid, flags + k, 1);
     if (tid == 0) {
-        int st = 2;
-        for (unsigned spins = 0; spins < VJF_SPIN_LIMIT; ++spins) {
-            const unsigned v = __hip_atomic_load(flags + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((v >> 1) == epoch) { st = (int)(v & 1u); break; }
-            if ((spins & 255u) == 255u && vjf_abort_seen(status)) break;
-            __builtin_amdgcn_s_sleep(4);
-        }
+        const int st = vjf_poll_flag<4>(flags + k, epoch, status);
         if (fence) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         s_ctl[0] = st;
     }
@@ -145,13 +129,7 @@ __device__ __forceinline__ void post_peek_columns(const unsigned* flags, unsigne
     if (tid == 0) {
         int st = 0, kr = from - 1;
         if (wait_first) {
-            st = 2;
-            for (unsigned spins = 0; spins < VJF_SPIN_LIMIT; ++spins) {
-                const unsigned v = __hip_atomic_load(flags + from, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((v >> 1) == epoch) { st = (int)(v & 1u); break; }
-                if ((spins & 255u) == 255u && vjf_abort_seen(status)) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
+            st = vjf_poll_flag<4>(flags + from, epoch, status);
             if (st == 0) kr = from;
         }
         if (st == 0)
@@ -197,7 +175,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
         if (tid == 0 && A.done) __hip_atomic_fetch_add(A.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
     const float* S = A.state;
-    const __amdgpu_buffer_rsrc_t r_L = post_rsrc(A.lscr, (size_t)n * n), r_dinv = post_rsrc(A.dinv, (size_t)nbl * 1024);
+    const __amdgpu_buffer_rsrc_t r_L = vjf_rsrc(A.lscr, (size_t)n * n), r_dinv = vjf_rsrc(A.dinv, (size_t)nbl * 1024);
     const int j0 = solve ? 0 : bix >> 1;                       // first block row of the substitution
     const int c0 = solve ? 0 : 16 * (bix & 1);
     auto tri = [](int bi, int bj) { return bi * (bi - 1) / 2 + bj; };       // strictly lower: bi > bj
@@ -258,16 +236,16 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int gi = min(bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, n - 1), gj = min(bj * 32 + c, n - 1);
-                gpre[q][r] = post_ld(G + (size_t)gi * n + gj);
+                gpre[q][r] = vjf_ld_sc1(G + (size_t)gi * n + gj);
             }
         }
     };
     // ... and, with g, what the operand role leaves beside it (sum |dx|^2, Phi^T dx) and the scalars of the state-noise update
     auto prefetch_rest = [&]() {
-        pre_sdx2 = post_ld(it_red + P.red_SC + RS_SDX2);
-        const float sig = post_ld(S + P.off[VJF_SLOT_TR_LOGVAR]);
+        pre_sdx2 = vjf_ld_sc1(it_red + P.red_SC + RS_SDX2);
+        const float sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);
         const float Bf = (float)A.B_total;
-        const float acc = fminf(post_ld(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_N_TR), 500.f);   // running_var, size_cap=500 (model.py:375)
+        const float acc = fminf(vjf_ld_sc1(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_N_TR), 500.f);   // running_var, size_cap=500 (model.py:375)
         pre_tot = acc + Bf;
         pre_old = (acc / pre_tot) * expf(sig);
         pre_scale = 1.0 / ((double)Bf * (double)P.dz);
@@ -275,7 +253,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
 #pragma unroll
         for (int q = 0; q < 8; ++q) {                                  // W's [row][16] grid: 224 * 16 <= 8 * 512
             const int e = tid + q * VJF_POST_THREADS, r = min(e >> 4, n - 1), cc = min(e & 15, dz - 1);
-            fpre[q] = post_ld(FDX + r * dz + cc);
+            fpre[q] = vjf_ld_sc1(FDX + r * dz + cc);
         }
     };
     auto prefetch_tail = [&]() { prefetch_G(); prefetch_rest(); };
@@ -301,7 +279,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
             const int it = 2 * q + bh;                                     // 0: Dinv_k; i = k + it: L block (i, k)
             const int gi = (k + it) * 32 + r, gj = k * 32 + c4;
             const bool real = it < nb && (it == 0 || (gi < n && gj < n));  // (padding rows / columns of L are zero)
-            v[q] = it == 0 ? post_ld4(r_dinv, real ? (size_t)k * 1024 + r * 32 + c4 : 0) : post_ld4(r_L, real ? (size_t)gi * n + gj : 0);
+            v[q] = it == 0 ? vjf_ld4_sc1(r_dinv, real ? (size_t)k * 1024 + r * 32 + c4 : 0) : vjf_ld4_sc1(r_L, real ? (size_t)gi * n + gj : 0);
         }                                                                  // (zeroed below, where they are stored: a select right behind a
 #pragma unroll                                                             //  load waits for it, and the four would go one after the other)
         for (int q = 0; q < 4; ++q) {
@@ -336,7 +314,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 // taken in as they appear while this workgroup waits for it
                 if (!g_there && A.fold_sigma) { prefetch_G(); g_pre = true; }
                 if (!g_there) {
-                    for (unsigned spins = 0;; ++spins) {
+                    for (unsigned spins = 0;; ++spins) {              // (the whole workgroup, a barrier per round: rounds of post_peek_columns, not one lane's poll)
                         post_peek_columns(A.flags, it_epoch, staged, nbl - 1, false, A.prep_count, it_prep_target, s_ctl, tid, A.status, A.acquire != 0);
                         const int st = s_ctl[0], kr = s_ctl[1], g = s_ctl[2];
                         __syncthreads();
@@ -344,7 +322,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                         for (int k2 = staged; k2 <= kr; ++k2) stage_column(k2);
                         if (kr >= staged) staged = kr + 1;
                         if (g) break;
-                        if (spins >= VJF_SPIN_LIMIT / 8 || ((spins & 63u) == 63u && vjf_abort_seen(A.status))) {
+                        if (spins >= VJF_WAIT_SPINS / 8 || ((spins & 63u) == 63u && vjf_abort_seen(A.status))) {
                             if (tid == 0) { vjf_status_or(A.status, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_G); *s_dead = 1; }
                             break;
                         }
@@ -356,7 +334,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 // statistics) is read behind the first column flag of this epoch: the flag says those kernels are complete.
                 for (int e = tid; e < nbl * 32 * 16; e += VJF_POST_THREADS) {
                     const int r = e >> 4, c = e & 15;
-                    s_x[r * LX + c] = (r < n && c < dz) ? post_ld(A.gbuf + (size_t)r * dz + c) : 0.f;
+                    s_x[r * LX + c] = (r < n && c < dz) ? vjf_ld_sc1(A.gbuf + (size_t)r * dz + c) : 0.f;
                 }
                 if (A.fold_sigma) { if (!g_pre) prefetch_G(); prefetch_rest(); }
             }
@@ -395,8 +373,10 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
     const bool k1_late = solve && A.fold_sigma && A.sig_word != nullptr;
     if (A.k1_done && !k1_late) {
         if (tid == 0) {
+            // (its own loop, not vjf_poll_count: as a call the compiler lays the tail's prefetches out twice -- 6 more sc1 loads in
+            //  vjf_mega_kernel, lane spills up in two pair kernels: profiles/handoff_header_isa.txt)
             int st = 2;
-            for (unsigned spins = 0; spins < VJF_SPIN_LIMIT; ++spins) {
+            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
                 const unsigned v = __hip_atomic_load(A.k1_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((int)(v - it_k1_target) >= 0) { st = 0; break; }
                 if ((spins & 255u) == 255u && vjf_abort_seen(A.status)) break;
@@ -422,7 +402,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 const int q0 = bix * per, q1 = min(nq, q0 + per);
                 for (int q = q0 + tid; q < q1; q += VJF_POST_THREADS) {
                     const int e = 4 * q, i = e / n, j = e - i * n;
-                    if ((j >> 5) <= (i >> 5)) *reinterpret_cast<float4*>(Ls + e) = post_ld4(r_L, (size_t)e);
+                    if ((j >> 5) <= (i >> 5)) *reinterpret_cast<float4*>(Ls + e) = vjf_ld4_sc1(r_L, (size_t)e);
                 }
             }
             // ---- w_chol[(j0*32 + c0 + c)][i] = X[i][c]: rows of w_chol, contiguous over i  (module.py:102)
@@ -435,8 +415,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 //  writes of the scalar form, beside the trial role's gradient slabs, which can leave at the same time)
                 for (int i = first + 4 * lane; i < n; i += 256) {
                     vjf_f32x4 o = {s_x[i * LX + c], s_x[(i + 1) * LX + c], s_x[(i + 2) * LX + c], s_x[(i + 3) * LX + c]};
-                    float* dstp = Wc + (size_t)gc * n + i;
-                    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dstp), "v"(o) : "memory");
+                    vjf_st4_wt(Wc + (size_t)gc * n + i, o);
                 }
             }
             if (A.xt) {
@@ -447,8 +426,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                     const int i = first + (e >> 2), q = (e & 3) * 4;
                     if (gc0 + q < n) {                                  // (n % 4 == 0)
                         vjf_f32x4 o = {s_x[i * LX + q], s_x[i * LX + q + 1], s_x[i * LX + q + 2], s_x[i * LX + q + 3]};
-                        float* dstp = A.xt + (size_t)i * n + gc0 + q;
-                        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dstp), "v"(o) : "memory");
+                        vjf_st4_wt(A.xt + (size_t)i * n + gc0 + q, o);
                     }
                 }
             }
@@ -514,7 +492,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
                 const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);
                 // (write-through: in the one-launch route the next step's operand workgroups, on other CUs, read these rows
                 //  with no kernel boundary in between)
-                for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_store_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));
+                for (int e = tid; e < n * n; e += VJF_POST_THREADS) vjf_st_wt(Pm + e, __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam));
             }
         }
         __syncthreads();
@@ -575,7 +553,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
             bool ok1 = true;
             if (k1_late && A.k1_done) {                        // sigma, the sample count and W of the state: behind their last readers
                 ok1 = false;
-                for (unsigned spins = 0; spins < VJF_SPIN_LIMIT; ++spins) {
+                for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {       // (its own loop, as the k1_done poll above and for the same reason)
                     const unsigned v = __hip_atomic_load(A.k1_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if ((int)(v - it_k1_target) >= 0) { ok1 = true; break; }
                     if ((spins & 255u) == 255u && vjf_abort_seen(A.status)) break;
@@ -609,7 +587,7 @@ __device__ __forceinline__ void vjf_rls_post_loop(const VjfPlan& P, const VjfPos
         const float* Wc = A.state + P.off[VJF_SLOT_W_CHOL];
         for (int e = bix * VJF_POST_THREADS + (int)threadIdx.x; e < n * n; e += nwg * VJF_POST_THREADS) {
             const int k = e / n, j = e - k * n;
-            vjf_store_wt(A.xt + (size_t)j * n + k, Wc[e]);
+            vjf_st_wt(A.xt + (size_t)j * n + k, Wc[e]);
         }
         vjf_wg_signal_wt(A.xt_count, (int)threadIdx.x);
     }
@@ -653,7 +631,7 @@ __global__ __launch_bounds__(VJF_CHOL_THREADS) void vjf_rls_pair_kernel(VjfPlan 
 // it cannot keep the single-workgroup chain kernels (which need a whole CU's LDS) from being placed.
 __global__ __launch_bounds__(64) void vjf_gate_kernel(const unsigned* count, unsigned target, float* status) {
     if (threadIdx.x != 0) return;
-    for (unsigned spins = 0; spins < VJF_SPIN_LIMIT; ++spins) {
+    for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {       // (its own loop, not vjf_poll_count: a wait given up elsewhere ends it without a bit of its own)
         const unsigned v = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((int)(v - target) >= 0) return;
         if ((spins & 255u) == 255u && vjf_abort_seen(status)) return;

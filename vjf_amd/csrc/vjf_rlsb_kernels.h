@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_chol_kernel.h"
+#include "vjf_handoff.h"
 #include "vjf_plan.h"
 
 struct VjfRlsbArgs {
@@ -34,21 +35,13 @@ struct VjfRlsbArgs {
 // drained before it counted itself in at the step barrier is read from memory, past this CU's L1 and this XCD's L2, with no
 // cache writeback or invalidate at the barrier (MI355X guide, "sc1 loads in place of the acquire").
 template <bool WT> __device__ __forceinline__ float rlsc_ld(const float* p) {
-    if (WT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
+    return WT ? vjf_ld_sc1(p) : *p;
 }
 template <bool WT> __device__ __forceinline__ void rlsc_st(float* p, float v) {
-    if (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
+    if (WT) vjf_st_wt(p, v); else *p = v;
 }
-typedef unsigned rlsc_u4 __attribute__((ext_vector_type(4)));
 template <bool WT> __device__ __forceinline__ float4 rlsc_ld4(const float* M, size_t off) {      // M: the same for the whole wavefront
-    if (WT) {
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(M), 0, 0x7fffffff, 0x00020000);
-        const rlsc_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 4), 0, 16);       // aux 16 = sc1
-        return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-    }
-    return *reinterpret_cast<const float4*>(M + off);
+    return WT ? vjf_ld4_sc1(vjf_rsrc(M), (int)off) : *reinterpret_cast<const float4*>(M + off);
 }
 
 // 32x32 tile (bi, bj) of the n x n row-major matrix M -> XOR-swizzled LDS tile; outside the matrix: the identity
@@ -335,14 +328,7 @@ __global__ __launch_bounds__(VJF_RLSC_THREADS) void vjf_rlsc_loop_kernel(VjfPlan
         __syncthreads();
         if (tid == 0) {
             __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned target = (unsigned)(k + 1) * gridDim.x;
-            bool there = false;
-            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-                if ((int)(__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) { there = true; break; }
-                if ((spins & 255u) == 255u && vjf_abort_seen(A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS)) break;
-                __builtin_amdgcn_s_sleep(VJF_RLSC_BARRIER_SLEEP);
-            }
-            s_go = there ? 1 : 0;
+            s_go = vjf_poll_count<VJF_RLSC_BARRIER_SLEEP>(bar, (unsigned)(k + 1) * gridDim.x, A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS) ? 1 : 0;
         }
         __syncthreads();
         // (a wait that ran out: a workgroup of this launch was never placed -- the update is dropped like one with a failed pivot, and,

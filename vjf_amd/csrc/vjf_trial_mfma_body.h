@@ -226,12 +226,7 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
         // W, w_chol, sigma come from the post kernel of the previous step on another stream: the host only lets this kernel
         // start once that kernel's workgroups are resident (vjf_prep_kernel's last workgroup checks), so the wait cannot starve it
         if (tid == 0) {
-            bool there = false;
-            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {
-                if ((int)(__hip_atomic_load(AA.rls_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - AA.rls_target) >= 0) { there = true; break; }
-                if ((spins & 255u) == 255u && vjf_abort_seen(A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS)) break;
-                __builtin_amdgcn_s_sleep(VJF_POLL_SLEEP);
-            }
+            const bool there = vjf_poll_count<VJF_POLL_SLEEP>(AA.rls_done, AA.rls_target, A.state + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS);
             if (!there) vjf_status_or(const_cast<float*>(A.state) + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_K1);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -13,6 +13,7 @@
 // w_chol is upper triangular (module.py:102), so variance tile j0 only runs k <= j0 + 15.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vjf_handoff.h"
 #include "vjf_plan.h"
 #include "vjf_trial_kernel.h"      // VjfTrialArgs, group_sum
 #include "vjf_act.h"
