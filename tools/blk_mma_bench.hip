@@ -2,7 +2,7 @@
 // alone and with all 8 wavefronts of the workgroup doing the same on their own blocks.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include "../vjf_amd/csrc/vjf_chol_kernel.h"
+#include "../vjf_amd/csrc/vjf_chol_blocks.h"
 #define NREP 16
 __global__ __launch_bounds__(512) void k(float* out, unsigned long long* t, int nw) {
     extern __shared__ __attribute__((aligned(16))) float lds[];

@@ -1,11 +1,11 @@
-// Diagnostic micro-benchmark (not part of the product): the streamed column chain (vjf_chol_kernel.h: potrf_inv_chain2_bcast on
+// Diagnostic micro-benchmark (not part of the product): the streamed column chain (chol_chain_variants.h: potrf_inv_chain2_bcast on
 // wavefront 0 = SIMD 0, potrf_follow on wavefront 1 = SIMD 1), checked against a host computation; cycles of the chain alone, of the
 // chain while it publishes, and when the follower is through (it starts DELAY cycles after the chain: the late join of the product).
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -o tools/chain_follow_bench tools/chain_follow_bench.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
-#include "../vjf_amd/csrc/vjf_chol_kernel.h"
+#include "chol_chain_variants.h"
 #define NREP 12
 __global__ __launch_bounds__(128) void k(const float* A, const float* Pn, const float* Nn, float* out, unsigned long long* t, int mode, int delay) {
     extern __shared__ float lds[];                     // (dynamic, carved by offsets as the product does)

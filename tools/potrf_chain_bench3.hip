@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
-#include "../vjf_amd/csrc/vjf_chol_kernel.h"
+#include "chol_chain_variants.h"
 
 __global__ void spin(float* out, int n) {
     float v = threadIdx.x;

@@ -23,8 +23,9 @@ NB = 32
 
 
 def potrf_inv_block(D):
-    """chol of a 32x32 tile with the inverse of its factor, column by column in fp32 (potrf_inv_chain2's arithmetic up to the
-    pairing of columns: pivot -> rsqrt -> scaled column -> rank-1 update of the tile and of the inverse's accumulator)."""
+    """chol of a 32x32 tile with the inverse of its factor, column by column in fp32 (the arithmetic of potrf_inv_chain2,
+    vjf_chol_blocks.h, up to the pairing of columns: pivot -> rsqrt -> scaled column -> rank-1 update of the tile and of the
+    inverse's accumulator)."""
     n = D.shape[0]
     A = D.astype(f32).copy()
     R = np.eye(n, dtype=f32)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/vjf_hip.h"
+#include "vjf_chol_blocks.h"
 #include "vjf_chol_kernel.h"
 #include "vjf_gram_kernel.h"
 #include "vjf_handoff.h"
@@ -23,6 +24,7 @@
 #include "vjf_ops_kernels.h"
 #include "vjf_plan.h"
 #include "vjf_post_kernel.h"
+#include "vjf_rls_operands.h"
 #include "vjf_rlsb_kernels.h"
 #include "vjf_serial_kernel.h"
 #include "vjf_trial_kernel.h"

@@ -1,10 +1,5 @@
 // vjf_chol_kernel.h -- fast path of the once-per-step serial half for n_rbf <= 224.
 //
-//   vjf_prep_kernel  (many workgroups): everything element-wise that the step's serial half
-//       needs -- finite guards + loss (model.py:138-154), clip + SGD (model.py:210-211),
-//       likelihood running variance (likelihood.py:28-40), g = P W + Phi^T dx / v and
-//       P += Phi^T Phi / v (module.py:94-96) -- so that ONE compute unit is left with nothing
-//       but the dependent chain.
 //   vjf_chol_lds_kernel (one workgroup, 8 wavefronts): L = chol(P) (module.py:99),
 //       W = P^-1 g (module.py:101), w_chol = L^-T (module.py:102), residual -> state-noise
 //       running variance (model.py:373-377).  The matrix lives in LDS as XOR-swizzled 32x32
@@ -14,628 +9,16 @@
 //       row j already spread over the lanes (column index on the lane), which is exactly the
 //       A- and B-operand layout, so a column step is  readlane(pivot) -> rsqrt -> scale -> MFMA
 //       with no cross-lane data movement.
+// (the operand / SGD kernels in front of it: vjf_rls_operands.h; the block primitives and the diagonal chain: vjf_chol_blocks.h)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vjf_chol_blocks.h"
 #include "vjf_gram_kernel.h"   // vjf_f32x16
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
 
 #define VJF_CHOL_THREADS 512
 #define VJF_CHOL_MAXBLK 7                 // n <= 224
-#define VJF_PREP_ROWS 1                   // rows of P per prep workgroup
-
-// ---------------------------------------------------------------------------------------------
-struct VjfPrepArgs {
-    float* state;
-    const float* red;
-    float* gbuf;          // (n, dz) g = P W + FDX / v
-    float* aux;           // transposed weight copies, kept in step with the SGD update
-    float* loss4;
-    int B_total;
-    unsigned flags;
-    int n_rowblk, n_sgdblk;
-    const unsigned* wait_count;   // vjf_prepg_kernel: non-null -> W, sigma come from a kernel on another stream: wait (bounded)
-    unsigned wait_target;         //   until *wait_count has reached wait_target, then acquire at agent scope
-    int bid0;             // first logical workgroup of this launch: 0 (whole grid, or the RLS-operand rows only)
-                          // or n_rowblk (SGD + scalars only) -- the two halves run on different streams in vjf_filter_seq
-    // scalar workgroup, vjf_filter_seq only: it ends only when this step's Cholesky kernel (run_word >= run_epoch) and all of its
-    // post kernel's workgroups (*start_count >= start_target) are RESIDENT.  The next backward half of the trial kernel waits
-    // in-kernel for their results: it must not take the CUs they need before they are placed.
-    const unsigned* run_word; unsigned run_epoch;
-    const unsigned* start_count; unsigned start_target;
-    unsigned* done_count;         // vjf_prepg_kernel: non-null -> += 1 per workgroup once its rows of P and g are in memory
-    // Non-finite loss component (vjf/model.py:138-149) on the one-stream route: the first pass leaves the parameters alone and
-    // writes the dropped components (bit 0 recon, 1 dynamics, 2 entropy; 0: nothing to replay) and the likelihood log-variance the
-    // step started with; the backward half and the gradient sums run again behind it (they return at once on 0), then the second
-    // pass (replay_pass) applies the step from the new sums.
-    unsigned* replay_mask; float* replay_rho; int replay_pass;
-};
-
-// logical grid = n_rowblk + n_sgdblk + 1
-__global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A) {
-    const int tid = threadIdx.x, bid = blockIdx.x + A.bid0;
-    float* S = A.state;
-    float* SC = S + P.off[VJF_SLOT_SCALARS];
-    const float* RSC = A.red + P.red_SCA;                      // the loss sums (RS_LRECON .. RS_SSEY)
-    const bool do_sgd = A.flags & VJF_FLAG_SGD, do_upd = A.flags & VJF_FLAG_UPDATE, warm = A.flags & VJF_FLAG_WARM_UP;
-    const float Bf = (float)A.B_total, invB = 1.0f / Bf;
-    float l_recon = RSC[RS_LRECON] * invB, l_dyn = RSC[RS_LDYN] * invB, ent = RSC[RS_ENT] * invB;
-    const bool ok_r = isfinite(l_recon), ok_d = isfinite(l_dyn), ok_h = isfinite(ent);
-    const bool grad_ok = ok_r && ok_h && (warm || ok_d);       // see vjf_serial_kernel / DESIGN.md
-    // some, not all, of the components in the loss are non-finite: the reference steps along the gradient of the others
-    const bool partial = do_sgd && !grad_ok && (ok_r || ok_h || (!warm && ok_d));
-    const bool replay = A.replay_mask != nullptr && partial;
-
-    if (bid < A.n_rowblk) {                                    // ---- RLS operands: one row of P per workgroup
-        if (!do_upd || warm) return;
-        __shared__ float s_part[4 * 32];
-        const int n = P.n, dz = P.dz, i = bid;
-        const float inv_v = expf(-S[P.off[VJF_SLOT_TR_LOGVAR]]);
-        const float lam = vjf_shrink_of(SC[VJF_SC_SHRINK]);
-        float* Pm = S + P.off[VJF_SLOT_W_PREC];
-        const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
-        const float* G = A.red + P.red_G;
-        const float* FDX = A.red + P.red_FDX;
-        // g[i][:] = sum_k lambda P[i][k] W[k][:] : thread k (n <= 224 < 256 on this path) holds one term per output,
-        // then wave + workgroup reduction
-        const int k = tid;
-        float p = 0.f;
-        if (k < n) {
-            p = vjf_lam_mul(Pm[(size_t)i * n + k], lam);                   // lambda P: of the update and of g = (lambda P) W
-            Pm[(size_t)i * n + k] = p + G[(size_t)i * n + k] * inv_v;      // P = lambda P + Phi^T Phi / v (module.py:96)
-        }
-        for (int j = 0; j < dz; ++j) {
-            float v = (k < n) ? p * Wm[(size_t)k * dz + j] : 0.f;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if ((tid & 63) == 0) s_part[(tid >> 6) * 32 + j] = v;
-        }
-        __syncthreads();
-        if (tid < dz) A.gbuf[(size_t)i * dz + tid] = ((s_part[tid] + s_part[32 + tid]) + s_part[64 + tid]) + s_part[96 + tid] + FDX[(size_t)i * dz + tid] * inv_v;
-        return;
-    }
-    if (bid < A.n_rowblk + A.n_sgdblk) {                       // ---- clip + SGD, tensor by tensor; transposed copies follow
-        if (A.replay_pass) { if (__hip_atomic_load(A.replay_mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return; }
-        else if (!(do_sgd && grad_ok)) return;
-        const float lr_dec = SC[VJF_SC_LR_DEC], lr_rec = SC[VJF_SC_LR_REC];
-        const bool freeze = SC[VJF_SC_FREEZE_DEC] != 0.f;
-        const int g0 = (bid - A.n_rowblk) * 256 + tid, gs = A.n_sgdblk * 256;
-        for (int t = 0; t < P.n_train; ++t) {
-            if (P.tr_dec[t] && freeze) continue;
-            const float lr = P.tr_dec[t] ? lr_dec : lr_rec;
-            const int rows = P.tr_rows[t], cols = P.tr_cols[t], off = P.tr_off[t];
-            for (int e = g0; e < rows * cols; e += gs) {
-                float g = A.red[off - P.train_off + e] * invB;
-                g = fminf(fmaxf(g, -1.f), 1.f);
-                const float w = S[off + e] - lr * g;
-                S[off + e] = w;
-                if (P.tr_aux[t] >= 0) {
-                    const int r = e / cols, c = e - r * cols;
-                    A.aux[P.tr_aux[t] + (size_t)c * P.tr_auxld[t] + P.tr_auxcol[t] + r] = w;
-                }
-            }
-        }
-        return;
-    }
-    if (A.replay_pass) return;                                 // (the scalars were settled by the first pass)
-    if (tid == 0) {                                            // ---- scalars: loss, likelihood log-variance
-        if (A.replay_mask) {
-            vjf_st_wt(A.replay_rho, S[P.off[VJF_SLOT_LIK_LOGVAR]]);
-            vjf_st_wt(A.replay_mask, replay ? ((ok_r ? 0u : 1u) | (ok_d ? 0u : 2u) | (ok_h ? 0u : 4u)) : 0u);
-        }
-        if (!ok_r) l_recon = 0.f;
-        if (!ok_d) l_dyn = 0.f;
-        if (!ok_h) ent = 0.f;
-        float loss = l_recon - ent;
-        if (!warm) loss += l_dyn;
-        if (A.loss4) { A.loss4[0] = loss; A.loss4[1] = -l_recon; A.loss4[2] = -l_dyn; A.loss4[3] = ent; }
-        const unsigned st = (ok_r ? 0u : VJF_STATUS_NONFINITE_RECON) | (ok_d ? 0u : VJF_STATUS_NONFINITE_DYN) |
-                            (ok_h ? 0u : VJF_STATUS_NONFINITE_ENT);
-        if (st) vjf_status_or(SC + VJF_SC_STATUS, st);
-        if (P.lik == VJF_LIK_GAUSSIAN) {
-            const float sse_y = RSC[RS_SSEY];
-            float rho = S[P.off[VJF_SLOT_LIK_LOGVAR]];
-            if (do_sgd && (grad_ok || (replay && ok_r))) {       // (its gradient comes from the reconstruction term alone)
-                float g = 0.5f * ((float)P.dy - expf(-rho) * sse_y * invB);
-                g = fminf(fmaxf(g, -1.f), 1.f);
-                rho -= SC[VJF_SC_LR_LIK] * g;
-            }
-            if (do_upd) {
-                const float mse = sse_y / (Bf * (float)P.dy);
-                const float acc = fminf(SC[VJF_SC_N_LIK], 1000.f), tot = acc + Bf;
-                rho = logf((acc / tot) * expf(rho) + (Bf / tot) * mse);
-                SC[VJF_SC_N_LIK] = tot;
-            }
-            S[P.off[VJF_SLOT_LIK_LOGVAR]] = rho;
-        }
-        if (A.run_word) {
-            bool there = false;
-            for (unsigned spins = 0; spins < VJF_WAIT_SPINS; ++spins) {      // (its own loop, not vjf_poll_count: two words, both there at the same look)
-                const unsigned r = __hip_atomic_load(A.run_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned q = __hip_atomic_load(A.start_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((int)(r - A.run_epoch) >= 0 && (int)(q - A.start_target) >= 0) { there = true; break; }
-                if ((spins & 255u) == 255u && vjf_abort_seen(SC + VJF_SC_STATUS)) break;
-                __builtin_amdgcn_s_sleep(2);
-            }
-            if (!there) vjf_status_or(SC + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_RESIDENT);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// RLS operands, 16 rows of P per workgroup (replaces the row part of vjf_prep_kernel on the fast path):
-//   g[i][:] = sum_k lambda P[i][k] W[k][:] + (Phi^T dx)[i][:] / v   (module.py:94)   on v_mfma_f32_16x16x4_f32, K split over 4 wavefronts
-//   P[i][:] = lambda P[i][:] + (Phi^T Phi)[i][:] / v                 (module.py:96)   on the rows just read
-// (lambda: the forgetting factor, VJF_SC_SHRINK; the rows are scaled once, as they arrive)
-// grid = ceil(n / 16) workgroups of 256 threads; n % 4 == 0.
-#define VJF_PREPG_LDP(n) ((n) + 4)
-static inline size_t vjf_prepg_lds_bytes(const VjfPlan& P) { return ((size_t)16 * VJF_PREPG_LDP(P.n) + (size_t)P.n * 17 + 4 * 16 * 17) * 4; }
-
-__global__ __launch_bounds__(256) void vjf_prepg_kernel(VjfPlan P, VjfPrepArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const unsigned do_upd = A.flags & VJF_FLAG_UPDATE, warm = A.flags & VJF_FLAG_WARM_UP;
-    if (!do_upd || warm) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = P.n, dz = P.dz, i0 = blockIdx.x * 16, ldp = VJF_PREPG_LDP(n);
-    float* s_p = lds;                                  // [16][n + 4]  rows of lambda P (P before the update)
-    float* s_w = s_p + 16 * ldp;                       // [n][17]      W, columns dz..15 zero
-    float* s_r = s_w + (size_t)n * 17;                 // [4][16][17]  per-wavefront partial products
-    float* S = A.state;
-    if (A.wait_count) {
-        if (tid == 0) {
-            const bool there = vjf_poll_count<4>(A.wait_count, A.wait_target, nullptr);
-            if (!there) vjf_status_or(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_OPERAND);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-    }
-    // (a vector load that bypasses L1 / the scalar cache: sigma may have been written while this kernel was already waiting)
-    const float inv_v = expf(-__hip_atomic_load(S + P.off[VJF_SLOT_TR_LOGVAR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const float lam = vjf_shrink_of(S[P.off[VJF_SLOT_SCALARS] + VJF_SC_SHRINK]);
-    float* Pm = S + P.off[VJF_SLOT_W_PREC];
-    const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
-    const float* G = A.red + P.red_G;
-    const float* FDX = A.red + P.red_FDX;
-    const int n4 = n >> 2;
-    for (int e0 = tid; e0 < 16 * n4; e0 += 4 * 256) {  // 4 float4 of P and of G in flight per thread
-        float4 p[4], g[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int e = e0 + q * 256, row = e / n4, c4 = (e - row * n4) * 4;
-            const bool in = e < 16 * n4 && i0 + row < n;
-            const size_t off = in ? (size_t)(i0 + row) * n + c4 : 0;
-            p[q] = *reinterpret_cast<const float4*>(Pm + off);
-            g[q] = *reinterpret_cast<const float4*>(G + off);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            p[q].x = vjf_lam_mul(p[q].x, lam); p[q].y = vjf_lam_mul(p[q].y, lam);
-            p[q].z = vjf_lam_mul(p[q].z, lam); p[q].w = vjf_lam_mul(p[q].w, lam);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int e = e0 + q * 256, row = e / n4, c4 = (e - row * n4) * 4;
-            if (e >= 16 * n4) continue;
-            const bool in = i0 + row < n;
-            float* d = s_p + row * ldp + c4;
-            d[0] = in ? p[q].x : 0.f; d[1] = in ? p[q].y : 0.f; d[2] = in ? p[q].z : 0.f; d[3] = in ? p[q].w : 0.f;
-            if (in) {
-                float4 o;
-                o.x = fmaf(g[q].x, inv_v, p[q].x); o.y = fmaf(g[q].y, inv_v, p[q].y); o.z = fmaf(g[q].z, inv_v, p[q].z); o.w = fmaf(g[q].w, inv_v, p[q].w);
-                float* dstp = Pm + (size_t)(i0 + row) * n + c4;
-                if (A.done_count) { vjf_st_wt(dstp, o.x); vjf_st_wt(dstp + 1, o.y); vjf_st_wt(dstp + 2, o.z); vjf_st_wt(dstp + 3, o.w); }
-                else *reinterpret_cast<float4*>(dstp) = o;
-            }
-        }
-    }
-    for (int e = tid; e < n * 16; e += 256) {
-        const int k = e >> 4, c = e & 15;
-        s_w[k * 17 + c] = c < dz ? Wm[(size_t)k * dz + c] : 0.f;
-    }
-    __syncthreads();
-    {
-        const int i = lane & 15, kk = lane >> 4;
-        vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int s4 = wave; s4 < n4; s4 += 4) {        // k-step s4 covers k = 4 s4 .. 4 s4 + 3
-            const float a = s_p[i * ldp + 4 * s4 + kk];
-            const float b = s_w[(4 * s4 + kk) * 17 + i];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s_r[(wave * 16 + 4 * (lane >> 4) + r) * 17 + (lane & 15)] = acc[r];   // row 4(lane>>4)+r, column lane&15
-    }
-    __syncthreads();
-    for (int e = tid; e < 16 * 16; e += 256) {
-        const int r = e >> 4, c = e & 15;
-        if (c < dz && i0 + r < n) {
-            const float v = ((s_r[r * 17 + c] + s_r[(16 + r) * 17 + c]) + s_r[(32 + r) * 17 + c]) + s_r[(48 + r) * 17 + c];
-            const float gv = v + FDX[(size_t)(i0 + r) * dz + c] * inv_v;
-            if (A.done_count) vjf_st_wt(A.gbuf + (size_t)(i0 + r) * dz + c, gv); else A.gbuf[(size_t)(i0 + r) * dz + c] = gv;
-        }
-    }
-    if (A.done_count) vjf_wg_signal_wt(A.done_count, tid);
-}
-
-// ---------------------------------------------------------------------------------------------
-// LDS block helpers.  A 32x32 block is 1024 floats; element (r,c) sits at r*32 + (c ^ r), which
-// makes row reads, column reads and the MFMA operand reads bank-conflict free.
-__device__ __forceinline__ int vsw(int r, int c) { return r * 32 + (c ^ r); }
-__device__ __forceinline__ int vtri(int bi, int bj) { return bi * (bi + 1) / 2 + bj; }
-// accumulator layout of v_mfma_f32_32x32x2_f32: column = lane & 31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-__device__ __forceinline__ int vrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-__device__ __forceinline__ float vrl(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ __forceinline__ float vrsqrt(float d) {               // rsqrt with one Newton step: ~0.5 ulp
-    float s = __builtin_amdgcn_rsqf(d);
-    return s * fmaf(-0.5f * d * s, s, 1.5f);
-}
-
-__device__ __forceinline__ void blk_load(vjf_f32x16& acc, const float* blk, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = blk[vsw(vrow(r, h), c)];
-}
-__device__ __forceinline__ void blk_load_t(vjf_f32x16& acc, const float* blk, int lane) {   // acc = blk^T
-    const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = blk[vsw(c, vrow(r, h))];
-}
-__device__ __forceinline__ void blk_store(const vjf_f32x16& acc, float* blk, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) blk[vsw(vrow(r, h), c)] = acc[r];
-}
-// acc += sign * Ab * Bb      (Bt: use Bb^T)
-template <bool Bt>
-__device__ __forceinline__ void blk_mma(vjf_f32x16& acc, const float* Ab, const float* Bb, float sign, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-    float a[16], b[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {                   // all 32 operand reads first ...
-        const int m = 2 * t + h;
-        a[t] = Ab[vsw(c, m)];
-        b[t] = Bt ? Bb[vsw(c, m)] : Bb[vsw(m, c)];
-    }
-    __builtin_amdgcn_sched_barrier(0);               // ... so the 16 MFMAs issue back to back
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sign * a[t], b[t], acc, 0, 0, 0);
-}
-
-// acc += A * B with operands given by functors: fa(i, m) = A[i][m], fb(m, j) = B[m][j]  (i, j = lane & 31)
-template <class FA, class FB>
-__device__ __forceinline__ void blk_mma_f(vjf_f32x16& acc, int lane, FA fa, FB fb) {
-    const int c = lane & 31, h = lane >> 5;
-    float a[16], b[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const int m = 2 * t + h;
-        a[t] = fa(c, m);
-        b[t] = fb(m, c);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[t], acc, 0, 0, 0);
-}
-
-// Cholesky of the symmetric tile held in `acc` (one wavefront) together with the inverse of its
-// factor: a second accumulator starts as I and receives the same column's rank-1 update
-// (R[c][:] -= L[c][j] * X[j][:]), so the two MFMAs of a step overlap in the pipe.
-// Writes L (lower part) into `out`, L^-1 (lower) into `inv`.  Returns false on a bad pivot.
-// Nothing but the dependent chain sits inside the column loop; the LDS stores follow it.
-__device__ __forceinline__ bool potrf_inv_chain(vjf_f32x16& acc, float* out, float* inv, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-    float lcol[32], xrow[32];
-    float dmin = 3.0e38f, slast = 1.f;
-    vjf_f32x16 racc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) racc[r] = (vrow(r, h) == c) ? 1.f : 0.f;
-    // Per column: readlane(pivot) -> rsq -> two scaled rows -> two MFMAs that share the A operand -l.
-    // (The inverse's update also clears its own row j -- R[j] -= L[j][j] X[j] = 0 -- which is never read again.)
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int rj = (j & 3) + 4 * (j >> 3), hj = (j >> 2) & 1;      // vrow(rj, hj) == j
-        const float d = vrl(acc[rj], j + 32 * hj);
-        const float s = __builtin_amdgcn_rsqf(d);
-        dmin = fminf(dmin, d);
-        slast = s;
-        // No per-column lane masks inside the chain: the A operand alone is zeroed on the other k half (which kills that
-        // k slot of both products), and entries left of the pivot -- rounding residue of earlier eliminations -- only
-        // reach rows / columns < j of the tiles, which are never read again.  The stores below mask.
-        const float l = acc[rj] * s;                                    // l[c] = L[c][j] for c >= j on half hj
-        const float x = racc[rj] * s;                                   // x[c] = Linv[j][c] on half hj
-        const float nl = (h == hj) ? -l : 0.f;
-        lcol[j] = l;
-        xrow[j] = x;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(nl, l, acc, 0, 0, 0);
-        racc = __builtin_amdgcn_mfma_f32_32x32x2f32(nl, x, racc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        if (h == hj) {
-            if (c >= j) out[vsw(c, j)] = lcol[j];
-            inv[vsw(j, c)] = (c <= j) ? xrow[j] : 0.f;
-        }
-    }
-    return (dmin > 0.f) && (slast == slast) && (fabsf(slast) < 3.0e38f);   // positive pivots, no NaN / inf came through
-}
-
-// Rank-2 form of the merged chain: two pivots per matrix-core round, so that BOTH k slots of v_mfma_f32_32x32x2 carry a
-// column (the rank-1 chain above zeroes one of them) -- 16 rounds of 2 MFMAs instead of 32 steps of 2.
-// The tile sits in the accumulator under a symmetric permutation: register r holds logical row 2r on lanes 0..31 and
-// logical row 2r + 1 on lanes 32..63 (physical row (r&3) + 8 (r>>2) + 4 half  <->  logical row 2r + half; same map for the
-// columns), so the two pivot rows of a round are the two halves of ONE register and land in the A / B operand layout
-// (k = lane >> 5) with no data movement; only column 2m scaled by its pivot has to cross to the other half once
-// (v_permlane32_swap) to update row 2m + 1 before its own pivot is taken.  A relabelling only: the factor is the lower
-// triangular L of the tile in the natural order.  Reads the tile from `dk`, writes L (lower) back and L^-1 (lower) to `inv`.
-__device__ __forceinline__ float vlo2both(float v) {            // lanes 0..31 of v on both halves
-    const unsigned u = __float_as_uint(v);
-    return __uint_as_float(__builtin_amdgcn_permlane32_swap(u, u, false, false)[0]);
-}
-// `nvalid`: rows / columns of the tile inside the matrix (the rest is the identity padding of the last block): a round whose two
-// pivots are padding would scale by 1 and update by 0 -- it is skipped (a uniform branch around the round: the loop stays fully
-// unrolled, every register index static), the result is the same bits.
-__device__ __forceinline__ bool potrf_inv_chain2(float* dk, float* inv, int lane, int nvalid = 32) {
-    const int c = lane & 31, h = lane >> 5;
-    const int lc = 2 * ((c & 3) + 4 * (c >> 3)) + ((c >> 2) & 1);   // logical column held by this lane
-    vjf_f32x16 acc, racc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lr = 2 * r + h;                                   // logical row of (register r, half h)
-        acc[r] = dk[vsw(lr, lc)];
-        racc[r] = (lr == lc) ? 1.f : 0.f;
-    }
-    float vcol[16], xcol[16];
-    float dmin = 3.0e38f, slast = 1.f;
-    const int rounds = (nvalid + 1) >> 1;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        vcol[m] = xcol[m] = (lc == 2 * m + h) ? 1.f : 0.f;          // (what a skipped round leaves: the identity)
-        if (m < rounds) {                                           // (uniform)
-        const int p1 = (m & 3) + 8 * (m >> 2), p2 = p1 + 4;         // physical columns of logical 2m and 2m + 1
-        const float d1 = vrl(acc[m], p1);                           // T[2m][2m]
-        const float q2 = vrl(acc[m], 32 + p2);                      // T[2m+1][2m+1], before column 2m is eliminated
-        const float s1 = __builtin_amdgcn_rsqf(d1);
-        const float l1 = acc[m] * s1;                               // lanes 0..31: L[.][2m]
-        const float e = vrl(l1, p2);                                // L[2m+1][2m]
-        const float t = fmaf(-e, vlo2both(l1), acc[m]);             // lanes 32..63: row 2m+1 with column 2m eliminated
-        const float d2 = fmaf(-e, e, q2);
-        const float s2 = __builtin_amdgcn_rsqf(d2);
-        const float v = h ? t * s2 : l1;                            // L[.][2m] | L[.][2m+1] by half = the k slot
-        const float x1 = racc[m] * s1;                              // lanes 0..31: Linv[2m][.]
-        const float x2 = fmaf(-e, vlo2both(x1), racc[m]) * s2;      // lanes 32..63: Linv[2m+1][.]
-        const float b = h ? x2 : x1;
-        const float nv = -v;
-        dmin = fminf(dmin, fminf(d1, d2));
-        slast = s2;
-        vcol[m] = v;
-        xcol[m] = b;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(nv, v, acc, 0, 0, 0);
-        racc = __builtin_amdgcn_mfma_f32_32x32x2f32(nv, b, racc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const int j = 2 * m + h;
-        if (lc >= j) dk[vsw(lc, j)] = vcol[m];
-        inv[vsw(j, lc)] = (lc <= j) ? xcol[m] : 0.f;
-    }
-    return (dmin > 0.f) && (slast == slast) && (fabsf(slast) < 3.0e38f);
-}
-
-// (Not on the product path either: `tools/chain_follow_bench.hip` and DESIGN.md section 3 "The streamed column chain" -- round 4 built the
-//  column loop on these two routines and measured it: correct, and no faster, because the first columns are bound by the helpers' bulk.)
-#ifndef VJF_FOLLOW_PHASE
-#define VJF_FOLLOW_PHASE 4                // rounds per phase of the follower wavefront (potrf_follow)
-#endif
-// ---- The streamed column chain: the chain wavefront publishes every round, a FOLLOWER wavefront on another SIMD rides on them.
-// A SIMD of this part runs either MFMA or VALU instructions, never both (tools/mfma_valu_overlap.hip: a wavefront's -- or its SIMD
-// neighbour's -- VALU work waits while a v_mfma_f32_32x32x2_f32 runs its 16 passes), so whatever else the chain wavefront does is added
-// to the dependent chain; what can ride on the chain's rounds belongs on another SIMD.  The follower applies round m of block column k
-//   * to T = tile (k+1,k), TRANSPOSED, in the chain's own register layout: the 2x2 step of the inverse's accumulator (same scalars
-//     s1, e, s2, same A operand -v): a forward substitution L_{k+1,k} = A_{k+1,k} L_kk^-T that ends with the chain, in place of the
-//     16-MFMA product with the finished inverse behind it;
-//   * to N = tile (k+1,k+1): the finished column pair of L_{k+1,k} is BOTH operands of one rank-2 update N -= l l^T -- the trailing
-//     update of the next diagonal block from registers, in place of a second 16-MFMA product through LDS.
-// The chain wavefront is left with its two MFMAs a round and three LDS stores: the pair of scaled columns (64 floats), the three
-// scalars, and -- one round later, when an s_waitcnt on them costs nothing -- the count of published rounds.
-// (the ring and its count are handed over as LDS-typed pointers: through generic ones hipcc's backend fails on this code with
-//  "Illegal instruction detected: Operand has incorrect register class ... $src_shared_base", DESIGN.md section 3 "Toolchain note")
-typedef __attribute__((address_space(3))) float vjf_lds_f;
-typedef __attribute__((address_space(3))) volatile int vjf_lds_vi;
-__device__ __forceinline__ bool potrf_inv_chain2_bcast(float* dk, float* inv, int lane, vjf_lds_f* ring_v, vjf_lds_f* ring_sc, vjf_lds_vi* rnd, const int rnd_base) {
-    const int c = lane & 31, h = lane >> 5;
-    const int lc = 2 * ((c & 3) + 4 * (c >> 3)) + ((c >> 2) & 1);   // logical column held by this lane
-    vjf_f32x16 acc, racc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int lr = 2 * r + h;                                   // logical row of (register r, half h)
-        acc[r] = dk[vsw(lr, lc)];
-        racc[r] = (lr == lc) ? 1.f : 0.f;
-    }
-    float vcol[16], xcol[16];
-    float dmin = 3.0e38f, slast = 1.f;
-    const int l3 = lane % 3;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const int p1 = (m & 3) + 8 * (m >> 2), p2 = p1 + 4;         // physical columns of logical 2m and 2m + 1
-        const float d1 = vrl(acc[m], p1);                           // T[2m][2m]
-        const float q2 = vrl(acc[m], 32 + p2);                      // T[2m+1][2m+1], before column 2m is eliminated
-        const float s1 = __builtin_amdgcn_rsqf(d1);
-        const float l1 = acc[m] * s1;                               // lanes 0..31: L[.][2m]
-        const float e = vrl(l1, p2);                                // L[2m+1][2m]
-        const float t = fmaf(-e, vlo2both(l1), acc[m]);             // lanes 32..63: row 2m+1 with column 2m eliminated
-        const float d2 = fmaf(-e, e, q2);
-        const float s2 = __builtin_amdgcn_rsqf(d2);
-        const float v = h ? t * s2 : l1;                            // L[.][2m] | L[.][2m+1] by half = the k slot
-        // Publish the round: every lane stores (no exec masks, no branches: lanes that share a word store the same value), and the
-        // count of round m - 1 goes out with round m's data -- the LDS executes a wavefront's instructions in order, and by now
-        // those stores are hundreds of cycles old anyway; nothing here waits.
-        if (m > 0) *rnd = rnd_base + m;
-        ring_v[m * 64 + lane] = v;
-        ring_sc[m * 3 + l3] = l3 == 0 ? s1 : l3 == 1 ? e : s2;
-        const float x1 = racc[m] * s1;                              // lanes 0..31: Linv[2m][.]
-        const float x2 = fmaf(-e, vlo2both(x1), racc[m]) * s2;      // lanes 32..63: Linv[2m+1][.]
-        const float b = h ? x2 : x1;
-        const float nv = -v;
-        dmin = fminf(dmin, fminf(d1, d2));
-        slast = s2;
-        vcol[m] = v;
-        xcol[m] = b;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(nv, v, acc, 0, 0, 0);
-        racc = __builtin_amdgcn_mfma_f32_32x32x2f32(nv, b, racc, 0, 0, 0);
-    }
-    *rnd = rnd_base + 16;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const int j = 2 * m + h;
-        if (lc >= j) dk[vsw(lc, j)] = vcol[m];
-        inv[vsw(j, lc)] = (lc <= j) ? xcol[m] : 0.f;
-    }
-    return (dmin > 0.f) && (slast == slast) && (fabsf(slast) < 3.0e38f);
-}
-// The follower's side: t1 = tile (k+1,k) (natural order, as panel_tile leaves it; L_{k+1,k} on return), n11 = tile (k+1,k+1) (updated on
-// return, where the next chain loads its block from).  Returns false if a published round did not come (`alive()` false or the bound).
-template <class AliveFn>
-__device__ __forceinline__ bool potrf_follow(float* t1, float* n11, int lane, const vjf_lds_f* ring_v, const vjf_lds_f* ring_sc, vjf_lds_vi* rnd, const int rnd_base, AliveFn alive) {
-    const int c = lane & 31, h = lane >> 5;
-    const int lc = 2 * ((c & 3) + 4 * (c >> 3)) + ((c >> 2) & 1);
-    vjf_f32x16 tacc, nacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        tacc[r] = t1[vsw(lc, 2 * r + h)];                           // T^T: row 2r + h = column 2r + h of the tile
-        nacc[r] = n11[vsw(2 * r + h, lc)];
-    }
-    // The rounds in PHASES of VJF_FOLLOW_PHASE: one poll for the phase's last round, its operands read together (one LDS round trip),
-    // then its rounds as straight-line code -- control flow between single rounds made the compiler park both accumulators in VGPRs at
-    // every join and sink the operand reads behind the poll (tools/chain_follow_bench.hip: 410 cycles a round against 150 here).  A
-    // follower that joins late (the product: its tiles arrive ~2 us into the chain) runs through the published phases without waiting;
-    // when the chain ends, at most one phase is left to do.
-    constexpr int PH = VJF_FOLLOW_PHASE;
-    float tcol[16];
-    bool ok = true;
-    unsigned spins = 0;
-#pragma unroll
-    for (int p0 = 0; p0 < 16; p0 += PH) {
-        while (ok && *rnd - rnd_base < p0 + PH) {                   // (uniform)
-            if ((++spins & 63u) == 0u && (spins > (1u << 22) || !alive())) ok = false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        asm volatile("" ::: "memory");
-        float vv[PH], s1v[PH], ev[PH], s2v[PH];
-#pragma unroll
-        for (int q = 0; q < PH; ++q) { const int j = p0 + q; vv[q] = ring_v[j * 64 + lane]; s1v[q] = ring_sc[j * 3]; ev[q] = ring_sc[j * 3 + 1]; s2v[q] = ring_sc[j * 3 + 2]; }
-#pragma unroll
-        for (int q = 0; q < PH; ++q) {
-            const int j = p0 + q;
-            const float y1 = tacc[j] * s1v[q];                              // lanes 0..31: L_{k+1,k}[.][2j]
-            const float y2 = fmaf(-ev[q], vlo2both(y1), tacc[j]) * s2v[q];   // lanes 32..63: L_{k+1,k}[.][2j+1]
-            const float y = h ? y2 : y1;
-            tcol[j] = y;
-            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(-vv[q], y, tacc, 0, 0, 0);
-            nacc = __builtin_amdgcn_mfma_f32_32x32x2f32(-y, y, nacc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < 16; ++m) t1[vsw(lc, 2 * m + h)] = tcol[m];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) n11[vsw(2 * r + h, lc)] = nacc[r];
-    return ok;
-}
-
-// (Not on the product path: kept for `tools/potrf_chain_bench3.hip`, which times the alternatives the rank-2 chain above was chosen
-//  against -- potrf alone 5088 cycles, inverse 4868, panel solve 4112, rank-2 chain with the inverse 5292.)
-// The same column chain split in three, so that each is a pure one-MFMA-per-step dependent chain (the merged chain
-// above pays the compiler's MFMA->VALU wait states twice per step: ~290 cycles/step against ~127 + ~94 + ~94 here)
-// and the inverse / the panel solves run on other wavefronts beside it.
-//   potrf_chain : L = chol(tile) -> out (lower part), pivot scales 1 / L[j][j] -> piv[0..32)
-//   inv_chain   : L^-1 (lower) -> inv, from L and the pivot scales (same arithmetic as the merged chain)
-//   trsm_chain  : in place  A_ik -> L_ik = A_ik L_kk^-T  by forward substitution on the transposed tile
-__device__ __forceinline__ bool potrf_chain(vjf_f32x16& acc, float* out, float* piv, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-    float lcol[32], sv[32];
-    float dmin = 3.0e38f;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int rj = (j & 3) + 4 * (j >> 3), hj = (j >> 2) & 1;      // vrow(rj, hj) == j
-        const float d = vrl(acc[rj], j + 32 * hj);
-        const float s = __builtin_amdgcn_rsqf(d);
-        dmin = fminf(dmin, d);
-        sv[j] = s;
-        const float l = acc[rj] * s;                                    // l[c] = L[c][j] for c >= j on half hj
-        const float nl = (h == hj) ? -l : 0.f;                          // (see potrf_inv_chain on the missing masks)
-        lcol[j] = l;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(nl, l, acc, 0, 0, 0);
-    }
-    float pv = 0.f;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        if (h == hj && c >= j) out[vsw(c, j)] = lcol[j];
-        pv = (lane == j) ? sv[j] : pv;
-    }
-    if (lane < 32) piv[lane] = pv;
-    const float slast = sv[31];
-    return (dmin > 0.f) && (slast == slast) && (fabsf(slast) < 3.0e38f);   // positive pivots, no NaN / inf came through
-}
-
-__device__ __forceinline__ void inv_chain(const float* Lk, const float* piv, float* inv, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-    float la[32], sv[32], xrow[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        const float l = Lk[vsw(c, j)];
-        la[j] = ((h == hj) && (c >= j)) ? -l : 0.f;
-        sv[j] = piv[j];
-    }
-    vjf_f32x16 racc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) racc[r] = (vrow(r, h) == c) ? 1.f : 0.f;
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int rj = (j & 3) + 4 * (j >> 3);
-        const float x = racc[rj] * sv[j];                               // x[c] = Linv[j][c] on half (j >> 2) & 1 (la is 0 on the other)
-        xrow[j] = x;
-        racc = __builtin_amdgcn_mfma_f32_32x32x2f32(la[j], x, racc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        if (h == hj) inv[vsw(j, c)] = (c <= j) ? xrow[j] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void trsm_chain(float* pb, const float* Lk, const float* piv, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-    float la[32], sv[32], lrow[32];
-    vjf_f32x16 acc;
-    blk_load_t(acc, pb, lane);                                          // acc = A_ik^T: row j of it is column j of A_ik
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        const float l = Lk[vsw(c, j)];
-        la[j] = ((h == hj) && (c > j)) ? -l : 0.f;
-        sv[j] = piv[j];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int rj = (j & 3) + 4 * (j >> 3);
-        const float b = acc[rj] * sv[j];                                // b[c] = L_ik[c][j] on half (j >> 2) & 1 (la is 0 on the other)
-        lrow[j] = b;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(la[j], b, acc, 0, 0, 0);   // A_ik^T[i][:] -= L_kk[i][j] L_ik[:][j], i > j
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const int hj = (j >> 2) & 1;
-        if (h == hj) pb[vsw(c, j)] = lrow[j];
-    }
-}
 
 struct VjfCholArgs {
     float* state;
@@ -682,12 +65,12 @@ struct VjfCholArgs {
     } while (0)
 
 static inline int vjf_chol_dzp(int dz) { return dz <= 4 ? 4 : dz <= 8 ? 8 : dz <= 12 ? 12 : dz <= 16 ? 16 : 32; }
-static inline size_t vjf_chol_lds_bytes(const VjfPlan& P) {
+static inline size_t vjf_chol_lds_bytes(const VjfPlan& P, int dzp) {            // dynamic LDS of vjf_chol_loop<dzp>
     const int nbl = (P.n + 31) / 32;
     const size_t blocks = (size_t)(nbl * (nbl + 1) / 2 + nbl) * 1024;
-    const int dzp = vjf_chol_dzp(P.dz);
     return (blocks + (size_t)nbl * 32 * dzp * (dzp <= 16 ? 1 : 2) + 192) * 4;   // dzp = 32: y = L^-1 g has a region of its own
 }
+static inline size_t vjf_chol_lds_bytes(const VjfPlan& P) { return vjf_chol_lds_bytes(P, vjf_chol_dzp(P.dz)); }
 static inline bool vjf_chol_lds_ok(const VjfPlan& P) {
     return (P.n + 31) / 32 <= VJF_CHOL_MAXBLK && P.n % 4 == 0 && P.dz <= 32 && vjf_chol_lds_bytes(P) <= 160 * 1024 - 512;
 }
@@ -703,6 +86,19 @@ __device__ __forceinline__ void axpy_row(float (&acc)[DZP], float x, const float
         acc[j] = fmaf(x, w.x, acc[j]); acc[j + 1] = fmaf(x, w.y, acc[j + 1]);
         acc[j + 2] = fmaf(x, w.z, acc[j + 2]); acc[j + 3] = fmaf(x, w.w, acc[j + 3]);
     }
+}
+
+// The lower block triangle is swept as float4 chunks, 256 per 32x32 block: chunk idx -> block, row in the block, first of its four columns
+__device__ __forceinline__ void chol_tile_of(int idx, int& b, int& r, int& c4) { b = idx >> 8; r = (idx >> 3) & 31; c4 = (idx & 7) * 4; }
+
+// The off-diagonal blocks on the other side of the diagonal (upper for w_pchol, lower for w_chol) are zero and stay zero: they
+// are cleared once per state blob (VJF_SC_TRI_CLEAN), not every step.  Element e of the (n, n) matrices.
+// (one element, not the sweep: as a routine that takes first element and stride, vjf_triclean_kernel needs 10 VGPRs for 8 --
+//  profiles/chol_split_isa.txt)
+__device__ __forceinline__ void chol_triclean_at(float* Lm, float* Wc, int n, int e) {
+    const int i = e / n, j = e - i * n;
+    if ((i >> 5) < (j >> 5)) Lm[e] = 0.f;
+    if ((i >> 5) > (j >> 5)) Wc[e] = 0.f;
 }
 
 template <int DZP>
@@ -767,7 +163,12 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     };
     if (warm) stat_wait();
 
+    // The phases below stay in this function: as routines of their own the intake, the column loop (one routine per kind of
+    // wavefront), the roll-back and the one-workgroup tail each put a kernel's lane-spill count above the parent's, and the
+    // state-noise tail moves code in eleven kernels, which no GPU run has timed (profiles/chol_split_isa.txt has the figures
+    // of every form that was tried).
     if (!warm) {
+        // ==== the intake
         // ---- load the lower block triangle of P_new (vjf_prep_kernel already added Phi^T Phi / v).  Wavefront 0 takes the
         //      first diagonal block alone and starts its column chain; the other seven bring in the rest meanwhile.
         //      All loads of a thread are issued before its first LDS store.
@@ -829,7 +230,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             const int idx = idx_of(q);
             v[q] = make_float4(0.f, 0.f, 0.f, 0.f); g[q] = v[q];
             if (idx < ntri * 256) {
-                const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                int b, r, c4; chol_tile_of(idx, b, r, c4);
                 const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
                 if (sp && !it_src_state) v[q] = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);
                 else v[q] = (gi < n && gj < n) ? *reinterpret_cast<const float4*>(Pm + (size_t)gi * n + gj) : pad4(gi, gj);
@@ -841,7 +242,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             for (int q = 0; q < NQ; ++q) {
                 const int idx = idx_of(q);
                 if (idx < ntri * 256) {
-                    const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                    int b, r, c4; chol_tile_of(idx, b, r, c4);
                     g[q] = g4(s_bi[b] * 32 + r, s_bj[b] * 32 + c4);
                 }
             }
@@ -862,7 +263,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         for (int q = 0; q < NQ; ++q) {
             const int idx = idx_of(q);
             if (idx < ntri * 256) {
-                const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                int b, r, c4; chol_tile_of(idx, b, r, c4);
                 float* blk = s_blk + (size_t)b * 1024;
                 blk[vsw(r, c4)] = v[q].x; blk[vsw(r, c4 + 1)] = v[q].y; blk[vsw(r, c4 + 2)] = v[q].z; blk[vsw(r, c4 + 3)] = v[q].w;
                 if (A.post) *reinterpret_cast<float4*>(A.pscr + (size_t)idx * 4) = v[q];
@@ -877,16 +278,9 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         __syncthreads();
         VJF_STAMP(1);
 
+        // ==== the column loop
         // ---- blocked right-looking Cholesky with look-ahead: while wavefronts 1..7 finish the trailing update of
         //      step k, wavefront 0 updates block (k+1,k+1) first and runs the next diagonal chain
-        auto trail = [&](int k, int t) {                                // A_ij -= L_ik L_jk^T for the t-th lower block
-            const int bi = k + 1 + s_bi[t], bj = k + 1 + s_bj[t];
-            float* cb = s_blk + (size_t)vtri(bi, bj) * 1024;
-            vjf_f32x16 acc;
-            blk_load(acc, cb, lane);
-            blk_mma<true>(acc, s_blk + (size_t)vtri(bi, k) * 1024, s_blk + (size_t)vtri(bj, k) * 1024, -1.f, lane);
-            blk_store(acc, cb, lane);
-        };
         // post mode: one finished 32x32 block out to global memory (one wavefront, 4 float4 per lane)
         // Write-through (sc1) 16-byte stores: the bytes are in memory, visible to every XCD, once the storing wavefront's vmcnt
         // has drained -- no release fence (cdna guide, Guideline 16 R1); the publishing code below drains them by hand (vjf_st4_wt).
@@ -1046,7 +440,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         __syncthreads();
         const bool ok = s_flag[0] != 0;
         VJF_STAMP(2);
-        if (!ok) {
+        if (!ok) {                                                      // ==== the roll-back of a failed factorisation
             // Reference: the fallback calls the removed torch.eig and raises (module.py:104-112).  Here:
             // undo P = lambda P + G / v (to rounding: (P' - G / v) / lambda) and leave W, w_chol, w_pchol as they were.
             st |= VJF_STATUS_RLS_FAILED;
@@ -1056,7 +450,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             if (!sp) for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) Pm[e] = __fdiv_rn(fmaf(-G[e], inv_v, Pm[e]), lam);
             if (A.post) {
                 for (int idx = tid; idx < ntri * 256; idx += VJF_CHOL_THREADS) {   // the copy for the next kernel, likewise
-                    const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                    int b, r, c4; chol_tile_of(idx, b, r, c4);
                     const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
                     if (gi < n && gj < n) {
                         float4 pv = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);
@@ -1075,11 +469,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             if (A.post) {
                 // L and the inverted diagonal blocks already left column by column; one-time clearing of the zero halves; done
                 if (!A.no_triclean && SC[VJF_SC_TRI_CLEAN] == 0.f) {
-                    for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) {
-                        const int i = e / n, j = e - i * n;
-                        if ((i >> 5) < (j >> 5)) Lm[e] = 0.f;
-                        if ((i >> 5) > (j >> 5)) Wc[e] = 0.f;
-                    }
+                    for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) chol_triclean_at(Lm, Wc, n, e);
                     __syncthreads();
                     if (tid == 0) SC[VJF_SC_TRI_CLEAN] = 1.f;
                 }
@@ -1087,6 +477,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 if (wave == 4) publish(VJF_CHOL_MAXBLK, VJF_CHOL_MAXBLK + 1, 0u);   // the factor as a whole is good
                 return;
             }
+            // ==== the one-workgroup tail (post == 0)
             // ---- w_pchol = L (lower, module.py:99-100)
             {
                 float4 v[VJF_CHOL_Q];
@@ -1094,7 +485,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 for (int q = 0; q < VJF_CHOL_Q; ++q) {
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
-                        const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                        int b, r, c4; chol_tile_of(idx, b, r, c4);
                         const float* blk = s_blk + (size_t)b * 1024;
                         const bool dg = s_bi[b] == s_bj[b];
                         v[q].x = (!dg || c4 <= r) ? blk[vsw(r, c4)] : 0.f;
@@ -1107,7 +498,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 for (int q = 0; q < VJF_CHOL_Q; ++q) {
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
-                        const int b = idx >> 8, r = (idx >> 3) & 31, c4 = (idx & 7) * 4;
+                        int b, r, c4; chol_tile_of(idx, b, r, c4);
                         const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
                         if (gi < n && gj < n) *reinterpret_cast<float4*>(Lm + (size_t)gi * n + gj) = v[q];
                     }
@@ -1156,7 +547,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 for (int q = 0; q < VJF_CHOL_Q; ++q) {
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
-                        const int b = idx >> 8, c = (idx >> 3) & 31, r4 = (idx & 7) * 4;
+                        int b, c, r4; chol_tile_of(idx, b, c, r4);
                         const float* blk = s_blk + (size_t)b * 1024;
                         const bool dg = s_bi[b] == s_bj[b];
                         v[q].x = (!dg || c <= r4) ? blk[vsw(r4, c)] : 0.f;
@@ -1169,20 +560,14 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 for (int q = 0; q < VJF_CHOL_Q; ++q) {
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
-                        const int b = idx >> 8, c = (idx >> 3) & 31, r4 = (idx & 7) * 4;
+                        int b, c, r4; chol_tile_of(idx, b, c, r4);
                         const int gi = s_bi[b] * 32 + r4, gj = s_bj[b] * 32 + c;          // X[gi..gi+3][gj]
                         if (gi < n && gj < n) *reinterpret_cast<float4*>(Wc + (size_t)gj * n + gi) = v[q];
                     }
                 }
             }
-            // The off-diagonal blocks on the other side of the diagonal (upper for w_pchol, lower for
-            // w_chol) are zero and stay zero; they are cleared once per state blob, not every step.
             if (SC[VJF_SC_TRI_CLEAN] == 0.f) {
-                for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) {
-                    const int i = e / n, j = e - i * n;
-                    if ((i >> 5) < (j >> 5)) Lm[e] = 0.f;
-                    if ((i >> 5) > (j >> 5)) Wc[e] = 0.f;
-                }
+                for (int e = tid; e < n * n; e += VJF_CHOL_THREADS) chol_triclean_at(Lm, Wc, n, e);
                 __syncthreads();
                 if (tid == 0) SC[VJF_SC_TRI_CLEAN] = 1.f;
             }
@@ -1222,11 +607,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                                               [&](int m, int j) { return j < DZP ? sb[m * DZP + j] : 0.f; });
                             }
                             store_part(acc, par == 0 ? s_pe : s_po, row);
-                        } else if (par == 1 && wave < nbl) {
-                            // (no odd partner row)
                         }
                     }
-                    // rows whose odd partial was not produced (nbl-1-w out of range never happens for w < nbl) are all covered
                     __syncthreads();
                     for (int e = tid; e < npad * DZP; e += VJF_CHOL_THREADS) {
                         const float v = s_pe[e] + s_po[e];
@@ -1249,6 +631,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         __syncthreads();
     }
     VJF_STAMP(7);
+    // ==== the state-noise tail
     // ---- residual mean square:  sum|dx|^2 - 2 tr(W^T FDX) + tr(W^T G W), fp64 accumulation (model.py:373-374).
     //      thread (i, part) forms half of row i of G W:  G row chunks as float4 (8 in flight), W rows broadcast
     double part_sum = 0.0;
@@ -1335,11 +718,7 @@ __global__ void vjf_triclean_kernel(VjfPlan P, float* state) {
     float* Wc = state + P.off[VJF_SLOT_W_CHOL];
     float* Lm = state + P.off[VJF_SLOT_W_PCHOL];
     const int n = P.n;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n * n; e += gridDim.x * blockDim.x) {
-        const int i = e / n, j = e - i * n;
-        if ((i >> 5) < (j >> 5)) Lm[e] = 0.f;
-        if ((i >> 5) > (j >> 5)) Wc[e] = 0.f;
-    }
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n * n; e += gridDim.x * blockDim.x) chol_triclean_at(Lm, Wc, n, e);
 }
 // (the flag is set by a second, one-thread launch behind it: every workgroup above must have seen it clear)
 __global__ void vjf_triclean_done_kernel(VjfPlan P, float* state) { state[P.off[VJF_SLOT_SCALARS] + VJF_SC_TRI_CLEAN] = 1.f; }

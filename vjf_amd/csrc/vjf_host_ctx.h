@@ -170,7 +170,7 @@ constexpr int kMegaRefused = 1 << 20;                  // filter_seq_mega: the g
 bool mega_plan_ok(const VjfPlan& P) {
     const int nbl = (P.n + 31) / 32;
     if (!vjf_chol_lds_ok(P) || P.dz > 16 || nbl > VJF_CHOL_MAXBLK) return false;          // LDS Cholesky loop + y / W and inverse loops
-    if ((size_t)(nbl * (nbl + 1) / 2 + nbl) * 1024 * 4 + (size_t)nbl * 32 * 16 * 4 + 768 > kMegaLds) return false;   // vjf_chol_loop<16>
+    if (vjf_chol_lds_bytes(P, 16) > kMegaLds) return false;                               // vjf_chol_loop<16>
     if (vjf_post_lds_bytes(P) > kMegaLds) return false;
     if ((size_t)vjf_mega_trial_lds(P).total * 4 > kMegaLds) return false;                 // 32 trials' working set
     if (vjf_mega_gram_lds_floats(P) * 4 > kMegaLds || vjf_mega_prep_lds_floats(P) * 4 > kMegaLds) return false;

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_chol_kernel.h"
+#include "vjf_rls_operands.h"   // VJF_PREPG_LDP
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
 #include "vjf_post_kernel.h"

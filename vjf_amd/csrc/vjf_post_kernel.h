@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
-#include "vjf_chol_kernel.h"         // VJF_CHOL_MAXBLK, vjf_f32x16
+#include "vjf_chol_kernel.h"         // VJF_CHOL_MAXBLK, VjfCholArgs, vjf_chol_loop
 #include "vjf_trial_mfma_kernel.h"   // vjf_f32x4
 
 #define VJF_POST_THREADS 512

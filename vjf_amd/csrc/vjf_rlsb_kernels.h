@@ -6,11 +6,11 @@
 //   nbl + 1 launches of vjf_rlsc_col_kernel: block column k of L (module.py:99) and block row k - 1 of X = L^-1 (module.py:102)
 //   two GEMMs (vjf_skinny_gemm_kernel)      y = X g,  W = X^T y                      (module.py:101)
 //   vjf_rlsb_final_kernel   w_chol = X^T, w_pchol = L, P += Phi^T Phi / v -- or, after a failed pivot, nothing but the status
-// All block products on v_mfma_f32_32x32x2_f32 through the helpers of vjf_chol_kernel.h.  Matrices are padded to a
+// All block products on v_mfma_f32_32x32x2_f32 through the helpers of vjf_chol_blocks.h.  Matrices are padded to a
 // multiple of 32 with the identity on the fly (loads) and never stored outside n x n.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_chol_kernel.h"
+#include "vjf_chol_blocks.h"
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
 

@@ -8,7 +8,7 @@
 // It leaves exactly what the fused kernels leave: rows of E / ACT / DEL, the posterior, per-workgroup loss partials.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_chol_kernel.h"   // vjf_f32x16, vrow
+#include "vjf_chol_blocks.h"   // vjf_f32x16, vrow
 #include "vjf_plan.h"
 #include "vjf_trial_kernel.h"  // VjfTrialArgs
 #include "vjf_act.h"
