@@ -2,7 +2,10 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--plot out.png]
+
+With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
+the +-2 sd band of the first latent at a few steps.
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -24,6 +27,7 @@ def main(argv=None):
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--n-rbf", type=int, default=100)
     ap.add_argument("--forecast", type=int, default=200)
+    ap.add_argument("--ensemble", type=int, default=0, help="members of the forecast with uncertainty (0: skip it), e.g. 64")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -39,10 +43,17 @@ def main(argv=None):
     t0 = time.perf_counter()
     m, logvar, loss = model.fit(y, max_iter=a.epochs)                                # posterior means / log-variances, last epoch's loss
     dt = time.perf_counter() - t0
+    q_last = vjf_amd.Gaussian(m[-1].detach(), logvar[-1].detach())                   # the last posterior, (1, 3) each
     m = m.detach().cpu().squeeze(1)
     print(f"fit: {a.epochs} epochs x {a.T} steps in {dt:.2f} s  ({a.epochs * a.T / dt:.0f} trial-timesteps/s), final epoch loss {float(loss):.4f}")
     xf, yf = model.forecast(x0=m[9:10], n_step=a.forecast, noise=False)              # (vjf/model.py:321-324)
     print("forecast:", tuple(xf.shape), tuple(yf.shape), "finite:", bool(torch.isfinite(xf).all() and torch.isfinite(yf).all()))
+    if a.ensemble > 0:
+        # forecast with uncertainty: sampled roll-outs from the last posterior in one native call, their mean and +-2 sd band
+        fe = model.forecast_ensemble(q_last, n_step=a.forecast, n_sample=a.ensemble, noise=True)
+        mean, sd = fe.x_mean[:, 0, 0].cpu(), fe.x_var[:, 0, 0].sqrt().cpu()
+        for t in sorted({0, a.forecast // 4, a.forecast // 2, a.forecast}):
+            print(f"ensemble forecast: step {t:4d}  x1 = {float(mean[t]):+.3f}  [{float(mean[t] - 2 * sd[t]):+.3f}, {float(mean[t] + 2 * sd[t]):+.3f}]")
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

@@ -268,6 +268,31 @@ int vjf_forecast_scratch_size(int32_t T, int32_t n, int32_t dout, int64_t* bytes
 int vjf_forecast_seq(const float* x0, const float* u, const float* w_noise, const float* s_noise, const float* centroid,
                      const float* logwidth, const float* w_mean, const float* w_chol, const float* tr_logvar, float* x,
                      void* scratch, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, void* stream);
+/* An ensemble of S roll-outs of RBFDS.forecast (vjf/model.py:342-361; every step draws its own weights, vjf/module.py:70-73, so
+ * one roll-out is one draw of the predictive distribution) and VJF.forecast's decoding of each (vjf/model.py:321-324), reduced to
+ * the per-step mean and population variance over the members, as one call.  Member s is vjf_forecast_seq on
+ * x0 + s * x0_member_stride, w_noise[s], s_noise[s], bit for bit; x0_member_stride (floats) is 0 for one start (B,dout) shared by
+ * the members or B * dout for x0 (S,B,dout).  w_noise (S,T,n,dout); s_noise (S,T,B,dout) or NULL; u (T,B,du) or NULL, shared.
+ * Out: x_mean, x_var (T+1,B,dout); y_mean, y_var (T+1,B,dy) of y = x dec_W^T + dec_b, dec_W (dy,dout) -- dec_W == NULL: no y
+ * outputs (dec_b, y_mean, y_var, dy are ignored); x_members (S,T+1,B,dout) or NULL: the members are not kept.  The decoded members
+ * never reach memory.  Every output element is folded over the members in member order (Welford, fp32) by one lane, so its bits
+ * depend on that trial's inputs alone; S = 1 gives the roll-out itself and variances of exactly 0.  T = 0: the moments of the starts
+ * (x_members is not written).  Asynchronous on `stream`, no host synchronisation; reads the state tensors, writes none.
+ * Members and steps run in chunks (three launches each) whose weight samples and states live in `scratch`:
+ * >= vjf_forecast_ens_scratch_size(T,S,B,n,dout) bytes, whatever T and S are at most 8 MiB of weight samples (+ four rows of
+ * padding; or one sample's n dout floats where that is more) + 32 MiB of member states (or two rows of B dout floats where that is
+ * more); a chunk is at most 4096 steps and 4096 members.  -1 null tensor, -20 bad shape, -21 u missing with d > dout, -11 n (d,
+ * dout) beyond one workgroup's LDS: all before the first launch. */
+int vjf_forecast_ens_scratch_size(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int64_t* bytes);
+/* The chunking vjf_forecast_ens takes for these sizes (VJF_FE_MEMBERS / VJF_FC_CHUNK included): members and steps per chunk.  A chunk
+ * needs members * steps * n * dout * 4 bytes of weight samples and members * (steps + 1) * B * dout * 4 bytes of states, both inside
+ * vjf_forecast_ens_scratch_size's bound for every T >= 1 and S (tests sweep it; the call checks it before its first launch). */
+int vjf_forecast_ens_chunks(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int32_t* members, int32_t* steps);
+int vjf_forecast_ens(const float* x0, int64_t x0_member_stride, const float* u, const float* w_noise, const float* s_noise,
+                     const float* centroid, const float* logwidth, const float* w_mean, const float* w_chol,
+                     const float* tr_logvar, const float* dec_W, const float* dec_b, float* x_mean, float* x_var,
+                     float* y_mean, float* y_var, float* x_members, void* scratch, int32_t T, int32_t S, int32_t B,
+                     int32_t n, int32_t d, int32_t dout, int32_t dy, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

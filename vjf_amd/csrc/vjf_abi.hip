@@ -468,6 +468,8 @@ __global__ __launch_bounds__(VJF_K1_THREADS) void vjf_blr_predict_kernel(VjfPred
 
 // the sampled roll-out of vjf_forecast_seq: vjf_fc_weights_kernel, vjf_fc_rollout_kernel
 #include "vjf_forecast_kernel.h"
+// the ensemble of roll-outs of vjf_forecast_ens: vjf_fe_weights_kernel, vjf_fe_rollout_kernel, vjf_fe_moments_kernel
+#include "vjf_forecast_ens_kernel.h"
 
 struct VjfRecArgs {
     const float* y; const float* u; const float* mu_s; const float* lv_s;
@@ -680,6 +682,175 @@ int vjf_forecast_seq(const float* x0, const float* u, const float* w_noise, cons
         else if (cl) launch(vjf_fc_rollout_kernel<0, true>);
         else launch(vjf_fc_rollout_kernel<0, false>);
         VJF_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+namespace {
+// Chunks of vjf_forecast_ens: Sc members x Tc steps whose weight samples take at most kFcScratchBytes and whose states (Tc + 1 rows
+// of B dout floats per member) at most kFeStateBytes; where one member-step is more than a cap, the chunk is that one member-step.
+// As many members side by side as the caps allow while a chunk keeps kFeMinChunk steps (a launch per chunk of steps is worth that
+// many), the member chunks levelled.  VJF_FE_MEMBERS / VJF_FC_CHUNK (tests) ask for fewer members / steps per chunk.
+constexpr size_t kFeStateBytes = (size_t)32 << 20;
+constexpr int kFeMaxMembers = 4096, kFeMinChunk = 16;
+struct FeChunks { int Sc, Tc; };
+FeChunks fe_chunks(int T, int S, int B, int n, int dout) {
+    const size_t wstep = (size_t)n * dout * 4, xstep = (size_t)B * dout * 4;
+    // steps per chunk that `sc` members leave room for: sc tc samples within kFcScratchBytes and sc (tc + 1) rows within
+    // kFeStateBytes; 0 where not even one step of `sc` members fits
+    auto steps = [&](int sc) {
+        const size_t w = kFcScratchBytes / wstep / sc, rows = kFeStateBytes / xstep / sc, x = rows > 1 ? rows - 1 : 0;
+        size_t t = w < x ? w : x;
+        t = t > (size_t)kFcMaxChunk ? (size_t)kFcMaxChunk : t;
+        return (int)(t > (size_t)T ? (size_t)T : t);
+    };
+    // members that `tc` steps leave room for (0: not one)
+    auto members = [&](int tc) {
+        const size_t w = kFcScratchBytes / wstep / tc, x = kFeStateBytes / xstep / ((size_t)tc + 1);
+        return w < x ? w : x;
+    };
+    const int want = T < kFeMinChunk ? T : kFeMinChunk;
+    int sc = S < kFeMaxMembers ? S : kFeMaxMembers;
+    if (steps(sc) < want) {                              // fewer members, so that a chunk keeps `want` steps; else as many as one step allows
+        size_t m = members(want);
+        if (m < 1) m = members(1);
+        sc = m < 1 ? 1 : (m < (size_t)sc ? (int)m : sc);
+    }
+    const int nch = (S + sc - 1) / sc;
+    sc = (S + nch - 1) / nch;
+    const char* me = getenv("VJF_FE_MEMBERS");
+    if (me && atoi(me) >= 1 && atoi(me) < sc) sc = atoi(me);
+    int tc = steps(sc);
+    if (tc < 1) tc = 1;                                  // (sc = 1 here: one member-step, more than a cap)
+    const char* ce = getenv("VJF_FC_CHUNK");
+    if (ce && atoi(ce) >= 1 && atoi(ce) < tc) tc = atoi(ce);
+    return FeChunks{sc, tc};
+}
+// min(a b per, cap), at least `least`, without overflow
+size_t fe_capped(int a, int64_t b, size_t per, size_t cap, size_t least) {
+    const size_t room = cap / per;
+    const size_t v = (size_t)a * (size_t)b <= room ? (size_t)a * (size_t)b * per : cap;
+    return v < least ? least : v;
+}
+// [weight samples of a chunk + four rows of padding (fc_scratch_bytes)] [states of a chunk]: whatever chunking the call takes
+size_t fe_w_bytes(int T, int S, int n, int dout) {
+    const size_t wstep = (size_t)n * dout * 4;
+    return (fe_capped(S, T, wstep, kFcScratchBytes, wstep) + (size_t)4 * dout * 4 + 255) / 256 * 256;
+}
+size_t fe_x_bytes(int T, int S, int B, int dout) {
+    const size_t xstep = (size_t)B * dout * 4;
+    return (fe_capped(S, (int64_t)T + 1, xstep, kFeStateBytes, 2 * xstep) + 255) / 256 * 256;
+}
+}  // namespace
+
+int vjf_forecast_ens_scratch_size(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int64_t* bytes) {
+    if (!bytes || T < 0 || S < 1 || B < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_ens_scratch_size: bad argument");
+    *bytes = (int64_t)(fe_w_bytes(T < 1 ? 1 : T, S, n, dout) + fe_x_bytes(T, S, B, dout));
+    return 0;
+}
+
+int vjf_forecast_ens_chunks(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int32_t* members, int32_t* steps) {
+    if (!members || !steps || T < 1 || S < 1 || B < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_ens_chunks: bad argument");
+    const FeChunks ch = fe_chunks(T, S, B, n, dout);
+    *members = ch.Sc; *steps = ch.Tc;
+    return 0;
+}
+
+int vjf_forecast_ens(const float* x0, int64_t x0_member_stride, const float* u, const float* w_noise, const float* s_noise,
+                     const float* centroid, const float* logwidth, const float* w_mean, const float* w_chol, const float* tr_logvar,
+                     const float* dec_W, const float* dec_b, float* x_mean, float* x_var, float* y_mean, float* y_var, float* x_members,
+                     void* scratch, int32_t T, int32_t S, int32_t B, int32_t n, int32_t d, int32_t dout, int32_t dy, void* stream) {
+    if (!x0 || !centroid || !logwidth || !w_mean || !w_chol || !x_mean || !x_var || !scratch || (T > 0 && !w_noise))
+        return fail(-1, "vjf_forecast_ens: null tensor");
+    if (dec_W && (!dec_b || !y_mean || !y_var)) return fail(-1, "vjf_forecast_ens: decoder without bias or y outputs");
+    if (T < 0 || S < 1 || B < 1 || n < 1 || dout < 1 || d < dout || (dec_W && dy < 1) ||
+        (x0_member_stride != 0 && x0_member_stride != (int64_t)B * dout))
+        return fail(-20, "vjf_forecast_ens: bad shape (T=%d S=%d B=%d n=%d d=%d dout=%d dy=%d, x0 member stride %lld)", T, S, B, n, d, dout,
+                    dy, (long long)x0_member_stride);
+    if (d > dout && !u && T > 0) return fail(-21, "vjf_forecast_ens: u is required when d > dout");
+    if (s_noise && !tr_logvar) return fail(-1, "vjf_forecast_ens: state noise without tr_logvar");
+    hipStream_t s = (hipStream_t)stream;
+    const int du = d - dout;
+    if (!dec_W) dy = 0;
+    if (vjf_fc_lds_floats(n, d, dout, false) * 4 > kMaxLds - 1024) return fail(-11, "vjf_forecast_ens: n=%d, d=%d too large", n, d);
+    // the forms of the roll-out as vjf_forecast_seq chooses them; VJF_FC_CENTROID_LDS=0 also takes the decoder out of LDS and
+    // VJF_FC_LOOKAHEAD=0 the batched staging out of the moments kernel (tests: the forms for large shapes, at any shape)
+    const bool cl = vjf_fc_lds_floats(n, d, dout, true) * 4 <= kMaxLds - 1024 && fc_env_on("VJF_FC_CENTROID_LDS");
+    const bool la = cl && n <= 64 * VJF_FC_KQ && dout <= 32 && fc_env_on("VJF_FC_LOOKAHEAD");
+    const int mb = vjf_fe_lds_floats(dout, VJF_FE_BATCH, false) * 4 <= kMaxLds / 4 && fc_env_on("VJF_FC_LOOKAHEAD") ? VJF_FE_BATCH : 1;
+    const bool dl = dy > 0 && vjf_fe_lds_floats(dout, mb, true) * 4 <= kMaxLds / 2 && fc_env_on("VJF_FC_CENTROID_LDS");
+    const size_t lds_m = vjf_fe_lds_floats(dout, mb, dl) * 4;
+    if (lds_m > kMaxLds - 1024) return fail(-11, "vjf_forecast_ens: dout=%d too large", dout);
+    const size_t lds = vjf_fc_lds_floats(n, d, dout, cl) * 4, lds_w = (size_t)n * VJF_LDT * 4;
+    const size_t wstep = (size_t)n * dout, xstep = (size_t)B * dout, ystep = (size_t)B * dy;
+    const int tiles = (B + 15) / 16, mt = (n + 15) / 16, zg = ((dout + 15) / 16 + (dy + 15) / 16 + VJF_FE_GROUP - 1) / VJF_FE_GROUP;
+
+    // rows r0 .. r0 + rows - 1 of the outputs from `rows` rows of states of members ms0 .. ms0 + Sc - 1
+    auto moments = [&](const float* xs, size_t xs_ms, int r0, int rows, int ms0, int Sc) {
+        VjfFeMomArgs m{};
+        m.xs = xs; m.xs_ms = xs_ms; m.dec_W = dec_W; m.dec_b = dec_b;
+        m.x_mean = x_mean + (size_t)r0 * xstep; m.x_var = x_var + (size_t)r0 * xstep;
+        m.y_mean = dy ? y_mean + (size_t)r0 * ystep : nullptr; m.y_var = dy ? y_var + (size_t)r0 * ystep : nullptr;
+        m.Sc = Sc; m.ms0 = ms0; m.S = S; m.last = ms0 + Sc == S; m.B = B; m.dout = dout; m.dy = dy; m.mb = mb;
+        if (dl) {
+            allow_lds(vjf_fe_moments_kernel<true>, lds_m);
+            hipLaunchKernelGGL(vjf_fe_moments_kernel<true>, dim3(tiles, rows, zg), dim3(VJF_FE_THREADS), lds_m, s, m);
+        } else {
+            allow_lds(vjf_fe_moments_kernel<false>, lds_m);
+            hipLaunchKernelGGL(vjf_fe_moments_kernel<false>, dim3(tiles, rows, zg), dim3(VJF_FE_THREADS), lds_m, s, m);
+        }
+    };
+    if (T == 0) {                                        // nothing to roll out: the moments of the starts (x_members is not written)
+        moments(x0, (size_t)x0_member_stride, 0, 1, 0, S);
+        VJF_HIP(hipGetLastError());
+        return 0;
+    }
+    const FeChunks ch = fe_chunks(T, S, B, n, dout);
+    if ((size_t)ch.Sc * ch.Tc * wstep * 4 + (size_t)4 * dout * 4 > fe_w_bytes(T, S, n, dout) ||
+        (size_t)ch.Sc * (ch.Tc + 1) * xstep * 4 > fe_x_bytes(T, S, B, dout))
+        return fail(-11, "vjf_forecast_ens: a chunk of %d members x %d steps is beyond the scratch", ch.Sc, ch.Tc);
+    float* W = (float*)scratch;
+    float* X = (float*)((char*)scratch + fe_w_bytes(T, S, n, dout));
+    // the members' states of a chunk: in x_members where they are kept, else in the scratch, (ch.Tc + 1) rows per member
+    const size_t xs_ms = x_members ? (size_t)(T + 1) * xstep : (size_t)(ch.Tc + 1) * xstep;
+    allow_lds(vjf_fe_weights_kernel, lds_w);
+    for (int32_t ms0 = 0; ms0 < S; ms0 += ch.Sc) {
+        const int Sc = S - ms0 < ch.Sc ? S - ms0 : ch.Sc;
+        int Tp = 0;                                      // steps of the previous chunk
+        for (int32_t t0 = 0; t0 < T; t0 += ch.Tc) {
+            const int Tc = T - t0 < ch.Tc ? T - t0 : ch.Tc;
+            VjfFeWeightArgs wa{w_mean, w_chol, w_noise + ((size_t)ms0 * T + t0) * wstep, W, (size_t)T * wstep, Sc, Tc, n, dout};
+            const int64_t nq = (int64_t)Sc * Tc;
+            int64_t gy = (nq + VJF_FC_WAVES - 1) / VJF_FC_WAVES, cap = 2048 / mt;
+            if (gy > cap) gy = cap;
+            if (gy < 1) gy = 1;
+            hipLaunchKernelGGL(vjf_fe_weights_kernel, dim3(mt, (unsigned)gy), dim3(VJF_FC_THREADS), lds_w, s, wa);
+            VJF_HIP(hipGetLastError());
+            // row 0 of the chunk's states is x[t0] (the start, or the previous chunk's last row), rows 1 .. Tc are x[t0 + 1 ..]
+            float* rows = x_members ? x_members + (size_t)ms0 * xs_ms + (size_t)t0 * xstep : X;
+            VjfFeArgs e{};
+            VjfFcArgs& a = e.a;
+            if (t0 == 0) { a.x_in = x0 + (size_t)ms0 * x0_member_stride; e.x_in_ms = (size_t)x0_member_stride; a.x0_out = rows; e.x0_out_ms = xs_ms; }
+            else { a.x_in = x_members ? rows : X + (size_t)Tp * xstep; e.x_in_ms = xs_ms; a.x0_out = nullptr; }
+            a.u = u ? u + (size_t)t0 * B * du : nullptr;
+            a.e = s_noise ? s_noise + ((size_t)ms0 * T + t0) * xstep : nullptr; e.e_ms = (size_t)T * xstep;
+            a.c = centroid; a.logw = logwidth; a.W = W; e.W_ms = (size_t)Tc * wstep; a.tr_logvar = tr_logvar;
+            a.x_out = rows + xstep; e.x_out_ms = xs_ms;
+            a.Tc = Tc; a.B = B; a.n = n; a.d = d; a.dout = dout;
+            auto launch = [&](auto kernel) {
+                allow_lds(kernel, lds);
+                hipLaunchKernelGGL(kernel, dim3(tiles, Sc), dim3(VJF_FC_THREADS), lds, s, e);
+            };
+            if (la && dout <= 16) launch(vjf_fe_rollout_kernel<1, true>);
+            else if (la) launch(vjf_fe_rollout_kernel<2, true>);
+            else if (cl) launch(vjf_fe_rollout_kernel<0, true>);
+            else launch(vjf_fe_rollout_kernel<0, false>);
+            VJF_HIP(hipGetLastError());
+            if (t0 == 0) moments(rows, xs_ms, 0, Tc + 1, ms0, Sc);
+            else moments(rows + xstep, xs_ms, t0 + 1, Tc, ms0, Sc);
+            VJF_HIP(hipGetLastError());
+            Tp = Tc;
+        }
     }
     return 0;
 }

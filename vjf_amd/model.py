@@ -20,6 +20,7 @@ import ctypes
 import logging
 import sys
 import weakref
+from collections import namedtuple
 from itertools import zip_longest
 from typing import Sequence, Tuple, Union
 
@@ -64,6 +65,11 @@ def _close_all():
 
 
 atexit.register(_close_all)
+
+
+# what VJF.forecast_ensemble returns: the per-step mean and population variance over the members of the latent state and of the
+# decoder's output, and the members' latent states (S, n_step + 1, B, xdim) or None
+ForecastEnsemble = namedtuple('ForecastEnsemble', ['x_mean', 'x_var', 'y_mean', 'y_var', 'x'])
 
 
 class LinearDecoder(Module):
@@ -128,6 +134,7 @@ class RBFDS(Module):
         self.register_parameter('logvar', Parameter(dev32(torch.tensor(0.), ndim2=False), requires_grad=False))
         self._n_sample = 0
         self._fc_scratch = None
+        self._fe_scratch = None
         object.__setattr__(self, '_owner', None)
         self._shrink = 1.
         self.shrink = shrink
@@ -268,6 +275,125 @@ class RBFDS(Module):
                                    N.ptr(vel.feature.logwidth), N.ptr(vel.w_mean), N.ptr(vel.w_chol), N.ptr(self.logvar), N.ptr(x),
                                    N.ptr(self._fc_scratch), T, B, n, d, dout, stream_ptr()), "vjf_forecast_seq")
         return x
+
+    def forecast_ensemble(self, x0: Union[Tensor, Gaussian], u: Tensor = None, n_step: int = 1, n_sample: int = 16, *,
+                          noise: bool = False, w_noise: Tensor = None, state_noise: Tensor = None, x0_noise: Tensor = None,
+                          return_members: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """`n_sample` independent sampled roll-outs of the whole horizon and their per-step mean and variance as ONE C-ABI call
+        (vjf_forecast_ens).  `forecast` draws fresh weights at every step, so one roll-out is one draw of the model's predictive
+        distribution; this is the distribution's first two moments.  Member s is exactly the roll-out `forecast_sequence` computes on
+        member s's draws.  The variance is the population one, sum (v - mean)^2 / S: exactly 0 with one member.
+        :param x0: (B, xdim), shared by the members; or (S, B, xdim), one start per member; or a Gaussian(mean, logvar), e.g. the
+            posterior `filter` returned: member s starts at mean + x0_noise[s] * exp(logvar / 2)
+        :param u: (n_step, B, udim), shared by the members
+        :param w_noise: (S, n_step, n_rbf, xdim);  :param state_noise: (S, n_step, B, xdim), implies `noise`;
+        :param x0_noise: (S, B, xdim), read only when x0 is a Gaussian
+        Draws that are not given follow the owning model's `noise`, as in `forecast_sequence`.  "device": one torch.randn per tensor
+        on the GPU.  "reference": the CPU generator, first x0_noise as one randn(S, B, xdim) (only for a Gaussian x0), then for member
+        0, 1, ... exactly `forecast`'s draws (per step the weight draw, then the state draw): with a plain x0 and a seed, the members
+        are bit for bit what S successive `forecast_sequence` calls under that seed return, and the generator ends in the same state.
+        :return: x_mean, x_var (n_step + 1, B, xdim) and the members x (S, n_step + 1, B, xdim) if `return_members`, else None
+        Asynchronous; reads the model's state and writes none.  The members' weight samples and states live in ONE bounded scratch
+        tensor kept on this module (like `_fc_scratch`): run one ensemble per model at a time -- calls on different streams must be
+        ordered by the caller, or go to different models."""
+        x_mean, x_var, _, _, x = self._forecast_ensemble(None, x0, u, n_step, n_sample, noise, w_noise, state_noise, x0_noise,
+                                                         return_members)
+        return x_mean, x_var, x
+
+    def _forecast_ensemble(self, decoder, x0, u, n_step, n_sample, noise, w_noise, state_noise, x0_noise, return_members):
+        """(x_mean, x_var, y_mean, y_var, x) of forecast_ensemble; the y moments are those of decoder(x) (None without a decoder)."""
+        S, T = int(n_sample), int(n_step)
+        if S < 1:
+            raise ValueError(f"n_sample must be at least 1, got {n_sample}")
+        assert T >= 0, 'n_step must not be negative'
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        reference = self._noise_mode() == "reference"
+        dt = torch.get_default_dtype()
+        if isinstance(x0, Gaussian):                       # the starts are formed here with torch ops: input handling, not hot path
+            mean, logvar = dev32(x0.mean), dev32(x0.logvar)
+            B, dout = mean.shape
+            assert logvar.shape == mean.shape
+            if x0_noise is None:
+                x0_noise = (dev32(torch.randn(S, B, dout, dtype=dt), ndim2=False) if reference
+                            else torch.randn(S, B, dout, device=mean.device, dtype=torch.float32))
+            else:
+                x0_noise = dev32(x0_noise, ndim2=False)
+                if x0_noise.ndim == 2 and B == 1:
+                    x0_noise = x0_noise[:, None, :]
+            assert x0_noise.shape == (S, B, dout)
+            x0 = (mean + x0_noise * torch.exp(.5 * logvar)).contiguous()
+        else:
+            x0 = dev32(x0, ndim2=False)
+            if x0.ndim < 3:
+                x0 = dev32(x0)
+        B, dout = x0.shape[-2:]
+        per_member = x0.ndim == 3
+        assert x0.ndim == 2 or x0.shape[0] == S, f"x0 has {x0.shape[0]} starts, expected n_sample={S}"
+        du = d - dout
+        assert dout == vel.n_output, f"x0 has {dout} columns, expected xdim={vel.n_output}"
+        if du > 0:
+            if u is None:
+                raise TypeError("u is required when udim > 0")
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == T, 'u must have length of n_step if present'
+            if u.ndim == 2 and B == 1:
+                u = u[:, None, :]
+            assert u.shape == (T, B, du)
+            u = u.contiguous()
+        else:
+            u = None
+        if w_noise is not None:
+            w_noise = dev32(w_noise, ndim2=False)
+            assert w_noise.shape == (S, T, n, dout)
+        if state_noise is not None:
+            state_noise = dev32(state_noise, ndim2=False)
+            if state_noise.ndim == 3 and B == 1:
+                state_noise = state_noise[:, :, None, :]
+            assert state_noise.shape == (S, T, B, dout)
+            state_noise = state_noise.contiguous()
+        want_w, want_s = w_noise is None and T > 0, state_noise is None and noise and T > 0
+        if want_w or want_s:
+            if reference:                                  # member by member, forecast's order within each (see forecast_sequence)
+                ws = []
+                ss = torch.empty(S, T, B, dout, dtype=dt, pin_memory=x0.is_cuda) if want_s else None
+                for m in range(S):
+                    for t in range(T):
+                        if want_w:
+                            ws.append(vel._draw_weight_noise())
+                        if want_s:
+                            torch.randn(B, dout, dtype=dt, out=ss[m, t])
+                if want_w:
+                    w_noise = dev32(torch.stack(ws).reshape(S, T, n, dout), ndim2=False)
+                if want_s:
+                    state_noise = ss.to(x0.device, torch.float32, non_blocking=True).contiguous()
+            else:
+                if want_w:
+                    w_noise = torch.randn(S, T, n, dout, device=x0.device, dtype=torch.float32)
+                if want_s:
+                    state_noise = torch.randn(S, T, B, dout, device=x0.device, dtype=torch.float32)
+        L = N.lib()
+        nbytes = ctypes.c_int64()
+        N.check(L.vjf_forecast_ens_scratch_size(T, S, B, n, dout, ctypes.byref(nbytes)), "vjf_forecast_ens_scratch_size")
+        if self._fe_scratch is None or self._fe_scratch.numel() < nbytes.value or self._fe_scratch.device != x0.device:   # (kept, grown on demand)
+            self._fe_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x0.device)
+        new = lambda *shape: torch.empty(*shape, device=x0.device, dtype=torch.float32)      # noqa: E731
+        x_mean, x_var = new(T + 1, B, dout), new(T + 1, B, dout)
+        W = b = y_mean = y_var = None
+        dy = 0
+        if decoder is not None:
+            W, b = decoder.decode.weight, decoder.decode.bias
+            dy = W.shape[0]
+            y_mean, y_var = new(T + 1, B, dy), new(T + 1, B, dy)
+        x = None
+        if return_members:                                 # (with no step to take the members are the starts)
+            x = new(S, T + 1, B, dout) if T > 0 else (x0 if per_member else x0.expand(S, B, dout))[:, None].clone()
+        N.check(L.vjf_forecast_ens(N.ptr(x0), B * dout if per_member else 0, N.ptr(u), N.ptr(w_noise), N.ptr(state_noise),
+                                   N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth), N.ptr(vel.w_mean), N.ptr(vel.w_chol),
+                                   N.ptr(self.logvar), N.ptr(W), N.ptr(b), N.ptr(x_mean), N.ptr(x_var), N.ptr(y_mean), N.ptr(y_var),
+                                   N.ptr(x) if T > 0 else None, N.ptr(self._fe_scratch), T, S, B, n, d, dout, dy, stream_ptr()),
+                "vjf_forecast_ens")
+        return x_mean, x_var, y_mean, y_var, x
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -919,3 +1045,15 @@ class VJF(Module):
         x = self.transition.forecast_sequence(x0, u, n_step, noise=noise, w_noise=w_noise, state_noise=state_noise)
         y = self.decoder(x)
         return x, y
+
+    def forecast_ensemble(self, x0: Union[Tensor, Gaussian], u: Tensor = None, n_step: int = 1, n_sample: int = 16, *,
+                          noise: bool = False, w_noise: Tensor = None, state_noise: Tensor = None, x0_noise: Tensor = None,
+                          return_members: bool = False) -> ForecastEnsemble:
+        """Forecast with uncertainty: `n_sample` sampled roll-outs of the whole horizon in one native call, reduced to the per-step
+        mean and population variance of the latent state x and of y (RBFDS.forecast_ensemble has the arguments and the draw order).
+        y is the decoder's output, exactly what `forecast` returns as y, for both likelihoods: under the Poisson likelihood it is the
+        linear predictor (the log rate), not the rate.  Every member is decoded on chip; no (S, n_step + 1, B, ydim) array is formed.
+        :return: ForecastEnsemble(x_mean, x_var (n_step + 1, B, xdim), y_mean, y_var (n_step + 1, B, ydim),
+                 x (S, n_step + 1, B, xdim) if `return_members` else None)"""
+        return ForecastEnsemble(*self.transition._forecast_ensemble(self.decoder, x0, u, n_step, n_sample, noise, w_noise, state_noise,
+                                                                    x0_noise, return_members))
