@@ -1,4 +1,4 @@
-// vjf_abi.hip -- extern "C" entry points declared in include/vjf_hip.h.  gfx950 only.
+// vjf_abi.hip -- extern "C" entry points declared in include/vjf_hip.h, no kernel and no launch (those: its vjf_host_*.h).  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -13,6 +13,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vjf_hip.h"
@@ -34,6 +35,8 @@
 #include "vjf_host_ctx.h"
 #include "vjf_host_launch.h"
 #include "vjf_host_routes.h"
+#include "vjf_host_ops.h"
+#include "vjf_host_forecast.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -400,190 +403,13 @@ int vjf_filter_seq(vjf_ctx* c, int32_t T, int32_t B, const float* y, const float
     return filter_seq_steps(c, T, s, flags, false);
 }
 
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// stand-alone operators
-// ------------------------------------------------------------------------------------------------
-namespace {
-inline dim3 grid1d(size_t n, int block = 256) { return dim3((unsigned)((n + block - 1) / block)); }
-// slot of the loss kernels' partial-sum table for this call (handed out in turn: VJF_LOSS_SLOTS calls may be in flight)
-inline int loss_slot() { static std::atomic<unsigned> next{0}; return (int)(next.fetch_add(1u, std::memory_order_relaxed) % VJF_LOSS_SLOTS); }
-
-struct VjfPredArgs {
-    const float* x; const float* c; const float* logw; const float* w_mean; const float* w_chol;
-    float* mean; float* logvar; int B, n, d, dout;
-};
-// 16 trials per workgroup: features feature-major in LDS ([feature][17], as the fused kernels hold them), then Phi W (mean)
-// and the row norm of Phi w_chol (logvar) as 16 x 16 output tiles on v_mfma_f32_16x16x4_f32 (mma_tile: the matrices are k-major
-// for these products), one tile per wavefront and round.
-__global__ __launch_bounds__(VJF_K1_THREADS) void vjf_blr_predict_kernel(VjfPredArgs A) {
-    constexpr int TB = 16, LD = VJF_LDT, NW = VJF_K1_THREADS / 64;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_phi = smem;                 // n x LD
-    float* s_red = s_phi + A.n * LD;     // NW x TB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b0 = blockIdx.x * TB, nb = min(TB, A.B - b0);
-    for (int i = tid; i < TB * A.n; i += VJF_K1_THREADS) {
-        const int k = i / TB, b = i - k * TB;
-        float ph = 0.f;
-        if (b < nb) {
-            float d2 = 0.f;
-            for (int j = 0; j < A.d; ++j) { const float t = A.x[(size_t)(b0 + b) * A.d + j] - A.c[(size_t)k * A.d + j]; d2 = fmaf(t, t, d2); }
-            const float w = expf(A.logw[k]);
-            ph = expf(-0.5f * d2 / (w * w));
-        }
-        s_phi[k * LD + b] = ph;
-    }
-    __syncthreads();
-    const int col = lane & 15, r4 = 4 * (lane >> 4);     // accumulator: row = r4 + r (output), column = trial
-    if (A.mean)
-        for (int t = wave; t * 16 < A.dout; t += NW) {
-            vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            mma_tile(acc, A.w_mean, A.dout, A.dout, t * 16, s_phi, A.n, lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = t * 16 + r4 + r;
-                if (j < A.dout && col < nb) A.mean[(size_t)(b0 + col) * A.dout + j] = acc[r];
-            }
-        }
-    if (!A.logvar) return;
-    float v2 = 0.f;                                      // this lane's share of sum_j Z[trial col][j]^2
-    for (int t = wave; t * 16 < A.n; t += NW) {
-        vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        mma_tile(acc, A.w_chol, A.n, A.n, t * 16, s_phi, A.n, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v2 = fmaf(acc[r], acc[r], v2);      // (rows beyond n are exact zeros)
-    }
-    v2 += __shfl_xor(v2, 16, 64);                        // the four row groups of a column, fixed order
-    v2 += __shfl_xor(v2, 32, 64);
-    if (lane < 16) s_red[wave * TB + lane] = v2;
-    __syncthreads();
-    for (int i = tid; i < nb * A.dout; i += VJF_K1_THREADS) {
-        const int b = i / A.dout;
-        float v = s_red[b];
-        for (int w = 1; w < NW; ++w) v += s_red[w * TB + b];
-        A.logvar[(size_t)(b0 + b) * A.dout + (i - b * A.dout)] = logf(v);
-    }
-}
-
-// the sampled roll-out of vjf_forecast_seq: vjf_fc_weights_kernel, vjf_fc_rollout_kernel
-#include "vjf_forecast_kernel.h"
-// the ensemble of roll-outs of vjf_forecast_ens: vjf_fe_weights_kernel, vjf_fe_rollout_kernel, vjf_fe_moments_kernel
-#include "vjf_forecast_ens_kernel.h"
-
-struct VjfRecArgs {
-    const float* y; const float* u; const float* mu_s; const float* lv_s;
-    const float* W[VJF_MAX_HIDDEN]; const float* b[VJF_MAX_HIDDEN];
-    const float* mean_W; const float* lv_W; const float* lv_b;
-    float* mu_t; float* lv_t;
-    int B, dy, du, dz, L; int h[VJF_MAX_HIDDEN];
-};
-// Recognition.forward for 16 trials per workgroup: activations feature-major in LDS (ping-pong), every layer as 16 x 16 output
-// tiles on v_mfma_f32_16x16x4_f32 with the weights read as torch stores them (mma_tile<true>).
-#define VJF_RECOGNITION_ACT 0
-#include "vjf_recognition_kernel.h"     // vjf_recognition_kernel
-#undef VJF_RECOGNITION_ACT
-#define VJF_RECOGNITION_ACT 1
-#include "vjf_recognition_kernel.h"     // vjf_recognition_act_kernel
-#undef VJF_RECOGNITION_ACT
-
-// features + target rows of the stand-alone RLS:  E[b] = [Phi(x_b) | target_b | 0]
-__global__ void vjf_rls_rows_kernel(const float* x, const float* c, const float* logw, const float* target, float* E,
-                                    int B, int n, int d, int dout, int ldE) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * ldE) return;
-    const int b = (int)(i / ldE), k = (int)(i - (size_t)b * ldE);
-    float v = 0.f;
-    if (k < n) {
-        float d2 = 0.f;
-        for (int j = 0; j < d; ++j) { const float t = x[(size_t)b * d + j] - c[(size_t)k * d + j]; d2 = fmaf(t, t, d2); }
-        const float w = expf(logw[k]);
-        v = expf(-0.5f * d2 / (w * w));
-    } else if (k < n + dout) {
-        v = target[(size_t)b * dout + (k - n)];
-    }
-    E[i] = v;
-}
-
-// plan for the stand-alone RLS (only the fields the Gram kernels read for kind-0 jobs)
-void rls_plan(int n, int dout, VjfPlan* P) {
-    memset(P, 0, sizeof *P);
-    P->n = n; P->dz = dout;
-    P->ldE = (int)vjf_align(n + dout, VJF_TILE);
-    P->red_SCA = 0; P->red_G = 0; P->red_FDX = n * n; P->red_SC = (int)vjf_align((int64_t)n * n + (int64_t)n * dout, 4);
-    P->red_len = P->red_SC + RS_N;
-}
-struct RlsCarve { size_t E, slabs, red, work, jobs, partial, total; int njobs, nsplit; };
-RlsCarve rls_carve(int B, int n, int dout, std::vector<VjfJob>* jobs_out) {
-    VjfPlan P; rls_plan(n, dout, &P);
-    std::vector<VjfJob> jobs; build_jobs(P, jobs);
-    // build_jobs also emits gradient jobs from the (zeroed) plan: keep kind 0 only
-    std::vector<VjfJob> k0;
-    for (auto& j : jobs) if (j.kind == 0) k0.push_back(j);
-    RlsCarve c{};
-    c.njobs = (int)k0.size(); c.nsplit = split_for(B);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
-    c.E = take((size_t)B * P.ldE * 4);
-    c.slabs = take((size_t)c.njobs * c.nsplit * 1024 * 4);
-    c.red = take((size_t)P.red_len * 4);
-    VjfPlan Q = P;
-    c.work = take(vjf_serial_work_floats(Q) * 4);
-    c.jobs = take(k0.size() * sizeof(VjfJob));
-    c.partial = take(RS_N * 4);
-    c.total = o;
-    if (jobs_out) *jobs_out = k0;
-    return c;
-}
-// Phi W (a.mean) and the row norm of Phi w_chol (a.logvar, or null) of vjf_blr_predict / vjf_blr_sample
-int launch_predict(const char* who, const VjfPredArgs& a, hipStream_t s) {
-    const size_t lds = ((size_t)a.n * VJF_LDT + 64) * 4;
-    if (lds > kMaxLds - 1024) return fail(-11, "%s: n=%d too large", who, a.n);
-    allow_lds(vjf_blr_predict_kernel, lds);
-    hipLaunchKernelGGL(vjf_blr_predict_kernel, dim3((a.B + 15) / 16), dim3(VJF_K1_THREADS), lds, s, a);
-    VJF_HIP(hipGetLastError());
-    return 0;
-}
-// the statistics of the stand-alone RLS / Kalman updates: rows [Phi | target] -> Gram tiles -> their reduction; G and Phi^T target are
-// then in the scratch's reduce buffer (*red_out), laid out as `P` (rls_plan) says
-int rls_statistics(const VjfPlan& P, void* scratch, const float* x, const float* centroid, const float* logwidth, const float* target,
-                   int B, int n, int d, int dout, hipStream_t s, RlsCarve* carve, float** red_out) {
-    std::vector<VjfJob> jobs;
-    const RlsCarve c = rls_carve(B, n, dout, &jobs);
-    char* ws = (char*)scratch;
-    VJF_HIP(hipMemcpyAsync(ws + c.jobs, jobs.data(), jobs.size() * sizeof(VjfJob), hipMemcpyHostToDevice, s));
-    VJF_HIP(hipStreamSynchronize(s));     // host vector goes out of scope
-    VJF_HIP(hipMemsetAsync(ws + c.partial, 0, RS_N * 4, s));
-    float* E = (float*)(ws + c.E);
-    hipLaunchKernelGGL(vjf_rls_rows_kernel, grid1d((size_t)B * P.ldE), dim3(256), 0, s, x, centroid, logwidth, target, E, B, n, d, dout, P.ldE);
-    VJF_HIP(hipGetLastError());
-    VjfGramArgs g{};
-    g.jobs = (const VjfJob*)(ws + c.jobs); g.E = E; g.ACT = E; g.DEL = E; g.slabs = (float*)(ws + c.slabs);
-    g.B = B; g.nsplit = c.nsplit; g.rows_per_split = ((B + c.nsplit - 1) / c.nsplit + 7) / 8 * 8;
-    hipLaunchKernelGGL(vjf_gram_kernel, dim3(c.njobs * c.nsplit), dim3(VJF_GRAM_THREADS), 0, s, P, g);
-    VJF_HIP(hipGetLastError());
-    VjfReduceArgs r{};
-    r.jobs = g.jobs; r.slabs = g.slabs; r.partial = (const float*)(ws + c.partial); r.red = (float*)(ws + c.red);
-    r.njobs = c.njobs; r.nsplit = c.nsplit; r.nblocks_k1 = 1;
-    hipLaunchKernelGGL(vjf_gram_reduce_kernel, dim3(c.njobs), dim3(VJF_REDUCE_THREADS), 0, s, P, r);   // sc_mask = 0: no loss sums here
-    VJF_HIP(hipGetLastError());
-    *carve = c; *red_out = r.red;
-    return 0;
-}
-}  // namespace
-
-extern "C" {
+// ---- stand-alone operators: argument checks, then one call (vjf_host_ops.h, vjf_host_forecast.h)
 
 int vjf_rbf_forward(const float* x, const float* centroid, const float* logwidth, float* out, int32_t B, int32_t n, int32_t d,
                     void* stream) {
     if (!x || !centroid || !logwidth || !out) return fail(-1, "vjf_rbf_forward: null tensor");
     if (B < 1 || n < 1 || d < 1) return fail(-20, "vjf_rbf_forward: bad shape");
-    const size_t lds = (size_t)16 * d * 4;
-    if (lds > kMaxLds - 1024) return fail(-11, "vjf_rbf_forward: d=%d too large", d);
-    allow_lds(vjf_rbf_kernel, lds);
-    hipLaunchKernelGGL(vjf_rbf_kernel, dim3((n + 255) / 256, (B + 15) / 16), dim3(256), lds, (hipStream_t)stream, x, centroid, logwidth, out, B, n, d);
-    VJF_HIP(hipGetLastError());
-    return 0;
+    return launch_rbf(x, centroid, logwidth, out, B, n, d, (hipStream_t)stream);
 }
 
 int vjf_blr_predict(const float* x, const float* centroid, const float* logwidth, const float* w_mean, const float* w_chol,
@@ -597,42 +423,13 @@ int vjf_blr_sample(const float* x, const float* centroid, const float* logwidth,
                    const float* noise, float* out, float* w_scratch, int32_t B, int32_t n, int32_t d, int32_t dout, void* stream) {
     if (!x || !centroid || !logwidth || !w_mean || !w_chol || !noise || !out || !w_scratch) return fail(-1, "vjf_blr_sample: null tensor");
     if (B < 1 || n < 1 || d < 1 || dout < 1) return fail(-20, "vjf_blr_sample: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    // w = w_mean + w_chol @ noise   (module.py:71)
-    {
-        VjfWideGemm g{};
-        g.A = w_chol; g.lda = n; g.Bm = noise; g.ldb = dout; g.C = w_scratch; g.ldc = dout; g.M = n; g.N = dout; g.K = n;
-        g.epi = WEPI_ADD_SRC; g.src = w_mean; g.lds = dout; g.src_scale = 1.f;
-        launch_wide_gemm(g, s);
-    }
+    VjfWideGemm g{};                                       // w = w_mean + w_chol @ noise   (module.py:71)
+    g.A = w_chol; g.lda = n; g.Bm = noise; g.ldb = dout; g.C = w_scratch; g.ldc = dout; g.M = n; g.N = dout; g.K = n;
+    g.epi = WEPI_ADD_SRC; g.src = w_mean; g.lds = dout; g.src_scale = 1.f;
+    launch_wide_gemm(g, (hipStream_t)stream);
     VJF_HIP(hipGetLastError());
-    return launch_predict("vjf_blr_sample", VjfPredArgs{x, centroid, logwidth, w_scratch, w_chol, out, nullptr, B, n, d, dout}, s);
+    return launch_predict("vjf_blr_sample", VjfPredArgs{x, centroid, logwidth, w_scratch, w_chol, out, nullptr, B, n, d, dout}, (hipStream_t)stream);
 }
-
-namespace {
-// Steps per chunk of vjf_forecast_seq: the weight samples of a chunk (n dout floats per step) take at most kFcScratchBytes, and a
-// chunk is at most kFcMaxChunk steps (a roll-out launch stays on the device for milliseconds, not seconds).  VJF_FC_CHUNK (tests)
-// asks for shorter chunks.
-constexpr size_t kFcScratchBytes = (size_t)8 << 20;
-constexpr int kFcMaxChunk = 4096;
-int fc_chunk_bound(int n, int dout) {
-    const size_t per = (size_t)n * dout * 4;
-    const size_t c = kFcScratchBytes / per;
-    return c < 1 ? 1 : (c > (size_t)kFcMaxChunk ? kFcMaxChunk : (int)c);
-}
-int fc_chunk(int n, int dout) {
-    const int bound = fc_chunk_bound(n, dout);
-    const char* ce = getenv("VJF_FC_CHUNK");
-    return ce && atoi(ce) >= 1 && atoi(ce) < bound ? atoi(ce) : bound;
-}
-// (four rows of padding behind the last W[t]: a wavefront whose share of K is shorter than 4 features -- n = 37: 12, 12, 12, 1 --
-//  hands mma_tile a K < 4, whose lanes kk >= K read row kb + kk, up to n + 2, from a valid address and mask the value)
-size_t fc_scratch_bytes(int T, int n, int dout) {
-    const int bound = fc_chunk_bound(n, dout);
-    return ((size_t)(T < bound ? T : bound) * n * dout * 4 + (size_t)4 * dout * 4 + 255) / 256 * 256;
-}
-bool fc_env_on(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0 && v[0] == '0'); }
-}  // namespace
 
 int vjf_forecast_scratch_size(int32_t T, int32_t n, int32_t dout, int64_t* bytes) {
     if (!bytes || T < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_scratch_size: bad argument");
@@ -647,101 +444,12 @@ int vjf_forecast_seq(const float* x0, const float* u, const float* w_noise, cons
     if (T < 1 || B < 1 || n < 1 || dout < 1 || d < dout) return fail(-20, "vjf_forecast_seq: bad shape (T=%d B=%d n=%d d=%d dout=%d)", T, B, n, d, dout);
     if (d > dout && !u) return fail(-21, "vjf_forecast_seq: u is required when d > dout");
     if (s_noise && !tr_logvar) return fail(-1, "vjf_forecast_seq: state noise without tr_logvar");
-    hipStream_t s = (hipStream_t)stream;
-    const int du = d - dout;
-    if (vjf_fc_lds_floats(n, d, dout, false) * 4 > kMaxLds - 1024) return fail(-11, "vjf_forecast_seq: n=%d, d=%d too large", n, d);
-    // VJF_FC_CENTROID_LDS=0 / VJF_FC_LOOKAHEAD=0 (tests): the forms for shapes beyond the LDS / register budgets, at any shape
-    const bool cl = vjf_fc_lds_floats(n, d, dout, true) * 4 <= kMaxLds - 1024 && fc_env_on("VJF_FC_CENTROID_LDS");
-    const bool la = cl && n <= 64 * VJF_FC_KQ && dout <= 32 && fc_env_on("VJF_FC_LOOKAHEAD");
-    const size_t lds = vjf_fc_lds_floats(n, d, dout, cl) * 4, lds_w = (size_t)n * VJF_LDT * 4;
-    const int mt = (n + 15) / 16, chunk = fc_chunk(n, dout);
-    float* W = (float*)scratch;
-    allow_lds(vjf_fc_weights_kernel, lds_w);
-    for (int32_t t0 = 0; t0 < T; t0 += chunk) {
-        const int Tc = T - t0 < chunk ? T - t0 : chunk;
-        VjfFcWeightArgs wa{w_mean, w_chol, w_noise + (size_t)t0 * n * dout, W, Tc, n, dout};
-        int gy = (Tc + VJF_FC_WAVES - 1) / VJF_FC_WAVES, cap = 2048 / mt;
-        if (gy > cap) gy = cap;
-        if (gy < 1) gy = 1;
-        hipLaunchKernelGGL(vjf_fc_weights_kernel, dim3(mt, gy), dim3(VJF_FC_THREADS), lds_w, s, wa);
-        VJF_HIP(hipGetLastError());
-        VjfFcArgs a{};
-        a.x_in = t0 == 0 ? x0 : x + (size_t)t0 * B * dout;
-        a.u = u ? u + (size_t)t0 * B * du : nullptr;
-        a.e = s_noise ? s_noise + (size_t)t0 * B * dout : nullptr;
-        a.c = centroid; a.logw = logwidth; a.W = W; a.tr_logvar = tr_logvar;
-        a.x0_out = t0 == 0 ? x : nullptr;
-        a.x_out = x + (size_t)(t0 + 1) * B * dout;
-        a.Tc = Tc; a.B = B; a.n = n; a.d = d; a.dout = dout;
-        auto launch = [&](auto kernel) {
-            allow_lds(kernel, lds);
-            hipLaunchKernelGGL(kernel, dim3((B + 15) / 16), dim3(VJF_FC_THREADS), lds, s, a);
-        };
-        if (la && dout <= 16) launch(vjf_fc_rollout_kernel<1, true>);
-        else if (la) launch(vjf_fc_rollout_kernel<2, true>);
-        else if (cl) launch(vjf_fc_rollout_kernel<0, true>);
-        else launch(vjf_fc_rollout_kernel<0, false>);
-        VJF_HIP(hipGetLastError());
-    }
-    return 0;
+    const FcForms fm = fc_forms(n, d, dout);
+    if (!fm.fits) return fail(-11, "vjf_forecast_seq: n=%d, d=%d too large", n, d);
+    VjfFcArgs a{};
+    a.u = u; a.c = centroid; a.logw = logwidth; a.tr_logvar = tr_logvar; a.B = B; a.n = n; a.d = d; a.dout = dout;
+    return forecast_run(a, w_mean, w_chol, x0, w_noise, s_noise, x, scratch, T, fm, fc_env_int("VJF_FC_CHUNK"), nullptr, (hipStream_t)stream);
 }
-
-namespace {
-// Chunks of vjf_forecast_ens: Sc members x Tc steps whose weight samples take at most kFcScratchBytes and whose states (Tc + 1 rows
-// of B dout floats per member) at most kFeStateBytes; where one member-step is more than a cap, the chunk is that one member-step.
-// As many members side by side as the caps allow while a chunk keeps kFeMinChunk steps (a launch per chunk of steps is worth that
-// many), the member chunks levelled.  VJF_FE_MEMBERS / VJF_FC_CHUNK (tests) ask for fewer members / steps per chunk.
-constexpr size_t kFeStateBytes = (size_t)32 << 20;
-constexpr int kFeMaxMembers = 4096, kFeMinChunk = 16;
-struct FeChunks { int Sc, Tc; };
-FeChunks fe_chunks(int T, int S, int B, int n, int dout) {
-    const size_t wstep = (size_t)n * dout * 4, xstep = (size_t)B * dout * 4;
-    // steps per chunk that `sc` members leave room for: sc tc samples within kFcScratchBytes and sc (tc + 1) rows within
-    // kFeStateBytes; 0 where not even one step of `sc` members fits
-    auto steps = [&](int sc) {
-        const size_t w = kFcScratchBytes / wstep / sc, rows = kFeStateBytes / xstep / sc, x = rows > 1 ? rows - 1 : 0;
-        size_t t = w < x ? w : x;
-        t = t > (size_t)kFcMaxChunk ? (size_t)kFcMaxChunk : t;
-        return (int)(t > (size_t)T ? (size_t)T : t);
-    };
-    // members that `tc` steps leave room for (0: not one)
-    auto members = [&](int tc) {
-        const size_t w = kFcScratchBytes / wstep / tc, x = kFeStateBytes / xstep / ((size_t)tc + 1);
-        return w < x ? w : x;
-    };
-    const int want = T < kFeMinChunk ? T : kFeMinChunk;
-    int sc = S < kFeMaxMembers ? S : kFeMaxMembers;
-    if (steps(sc) < want) {                              // fewer members, so that a chunk keeps `want` steps; else as many as one step allows
-        size_t m = members(want);
-        if (m < 1) m = members(1);
-        sc = m < 1 ? 1 : (m < (size_t)sc ? (int)m : sc);
-    }
-    const int nch = (S + sc - 1) / sc;
-    sc = (S + nch - 1) / nch;
-    const char* me = getenv("VJF_FE_MEMBERS");
-    if (me && atoi(me) >= 1 && atoi(me) < sc) sc = atoi(me);
-    int tc = steps(sc);
-    if (tc < 1) tc = 1;                                  // (sc = 1 here: one member-step, more than a cap)
-    const char* ce = getenv("VJF_FC_CHUNK");
-    if (ce && atoi(ce) >= 1 && atoi(ce) < tc) tc = atoi(ce);
-    return FeChunks{sc, tc};
-}
-// min(a b per, cap), at least `least`, without overflow
-size_t fe_capped(int a, int64_t b, size_t per, size_t cap, size_t least) {
-    const size_t room = cap / per;
-    const size_t v = (size_t)a * (size_t)b <= room ? (size_t)a * (size_t)b * per : cap;
-    return v < least ? least : v;
-}
-// [weight samples of a chunk + four rows of padding (fc_scratch_bytes)] [states of a chunk]: whatever chunking the call takes
-size_t fe_w_bytes(int T, int S, int n, int dout) {
-    const size_t wstep = (size_t)n * dout * 4;
-    return (fe_capped(S, T, wstep, kFcScratchBytes, wstep) + (size_t)4 * dout * 4 + 255) / 256 * 256;
-}
-size_t fe_x_bytes(int T, int S, int B, int dout) {
-    const size_t xstep = (size_t)B * dout * 4;
-    return (fe_capped(S, (int64_t)T + 1, xstep, kFeStateBytes, 2 * xstep) + 255) / 256 * 256;
-}
-}  // namespace
 
 int vjf_forecast_ens_scratch_size(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int64_t* bytes) {
     if (!bytes || T < 0 || S < 1 || B < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_ens_scratch_size: bad argument");
@@ -751,7 +459,7 @@ int vjf_forecast_ens_scratch_size(int32_t T, int32_t S, int32_t B, int32_t n, in
 
 int vjf_forecast_ens_chunks(int32_t T, int32_t S, int32_t B, int32_t n, int32_t dout, int32_t* members, int32_t* steps) {
     if (!members || !steps || T < 1 || S < 1 || B < 1 || n < 1 || dout < 1) return fail(-20, "vjf_forecast_ens_chunks: bad argument");
-    const FeChunks ch = fe_chunks(T, S, B, n, dout);
+    const FeChunks ch = fe_chunks(T, S, B, n, dout, fc_env_int("VJF_FE_MEMBERS"), fc_env_int("VJF_FC_CHUNK"));
     *members = ch.Sc; *steps = ch.Tc;
     return 0;
 }
@@ -769,90 +477,18 @@ int vjf_forecast_ens(const float* x0, int64_t x0_member_stride, const float* u, 
                     dy, (long long)x0_member_stride);
     if (d > dout && !u && T > 0) return fail(-21, "vjf_forecast_ens: u is required when d > dout");
     if (s_noise && !tr_logvar) return fail(-1, "vjf_forecast_ens: state noise without tr_logvar");
-    hipStream_t s = (hipStream_t)stream;
-    const int du = d - dout;
     if (!dec_W) dy = 0;
-    if (vjf_fc_lds_floats(n, d, dout, false) * 4 > kMaxLds - 1024) return fail(-11, "vjf_forecast_ens: n=%d, d=%d too large", n, d);
-    // the forms of the roll-out as vjf_forecast_seq chooses them; VJF_FC_CENTROID_LDS=0 also takes the decoder out of LDS and
-    // VJF_FC_LOOKAHEAD=0 the batched staging out of the moments kernel (tests: the forms for large shapes, at any shape)
-    const bool cl = vjf_fc_lds_floats(n, d, dout, true) * 4 <= kMaxLds - 1024 && fc_env_on("VJF_FC_CENTROID_LDS");
-    const bool la = cl && n <= 64 * VJF_FC_KQ && dout <= 32 && fc_env_on("VJF_FC_LOOKAHEAD");
-    const int mb = vjf_fe_lds_floats(dout, VJF_FE_BATCH, false) * 4 <= kMaxLds / 4 && fc_env_on("VJF_FC_LOOKAHEAD") ? VJF_FE_BATCH : 1;
-    const bool dl = dy > 0 && vjf_fe_lds_floats(dout, mb, true) * 4 <= kMaxLds / 2 && fc_env_on("VJF_FC_CENTROID_LDS");
-    const size_t lds_m = vjf_fe_lds_floats(dout, mb, dl) * 4;
-    if (lds_m > kMaxLds - 1024) return fail(-11, "vjf_forecast_ens: dout=%d too large", dout);
-    const size_t lds = vjf_fc_lds_floats(n, d, dout, cl) * 4, lds_w = (size_t)n * VJF_LDT * 4;
-    const size_t wstep = (size_t)n * dout, xstep = (size_t)B * dout, ystep = (size_t)B * dy;
-    const int tiles = (B + 15) / 16, mt = (n + 15) / 16, zg = ((dout + 15) / 16 + (dy + 15) / 16 + VJF_FE_GROUP - 1) / VJF_FE_GROUP;
-
-    // rows r0 .. r0 + rows - 1 of the outputs from `rows` rows of states of members ms0 .. ms0 + Sc - 1
-    auto moments = [&](const float* xs, size_t xs_ms, int r0, int rows, int ms0, int Sc) {
-        VjfFeMomArgs m{};
-        m.xs = xs; m.xs_ms = xs_ms; m.dec_W = dec_W; m.dec_b = dec_b;
-        m.x_mean = x_mean + (size_t)r0 * xstep; m.x_var = x_var + (size_t)r0 * xstep;
-        m.y_mean = dy ? y_mean + (size_t)r0 * ystep : nullptr; m.y_var = dy ? y_var + (size_t)r0 * ystep : nullptr;
-        m.Sc = Sc; m.ms0 = ms0; m.S = S; m.last = ms0 + Sc == S; m.B = B; m.dout = dout; m.dy = dy; m.mb = mb;
-        if (dl) {
-            allow_lds(vjf_fe_moments_kernel<true>, lds_m);
-            hipLaunchKernelGGL(vjf_fe_moments_kernel<true>, dim3(tiles, rows, zg), dim3(VJF_FE_THREADS), lds_m, s, m);
-        } else {
-            allow_lds(vjf_fe_moments_kernel<false>, lds_m);
-            hipLaunchKernelGGL(vjf_fe_moments_kernel<false>, dim3(tiles, rows, zg), dim3(VJF_FE_THREADS), lds_m, s, m);
-        }
-    };
-    if (T == 0) {                                        // nothing to roll out: the moments of the starts (x_members is not written)
-        moments(x0, (size_t)x0_member_stride, 0, 1, 0, S);
-        VJF_HIP(hipGetLastError());
-        return 0;
-    }
-    const FeChunks ch = fe_chunks(T, S, B, n, dout);
-    if ((size_t)ch.Sc * ch.Tc * wstep * 4 + (size_t)4 * dout * 4 > fe_w_bytes(T, S, n, dout) ||
-        (size_t)ch.Sc * (ch.Tc + 1) * xstep * 4 > fe_x_bytes(T, S, B, dout))
-        return fail(-11, "vjf_forecast_ens: a chunk of %d members x %d steps is beyond the scratch", ch.Sc, ch.Tc);
-    float* W = (float*)scratch;
-    float* X = (float*)((char*)scratch + fe_w_bytes(T, S, n, dout));
-    // the members' states of a chunk: in x_members where they are kept, else in the scratch, (ch.Tc + 1) rows per member
-    const size_t xs_ms = x_members ? (size_t)(T + 1) * xstep : (size_t)(ch.Tc + 1) * xstep;
-    allow_lds(vjf_fe_weights_kernel, lds_w);
-    for (int32_t ms0 = 0; ms0 < S; ms0 += ch.Sc) {
-        const int Sc = S - ms0 < ch.Sc ? S - ms0 : ch.Sc;
-        int Tp = 0;                                      // steps of the previous chunk
-        for (int32_t t0 = 0; t0 < T; t0 += ch.Tc) {
-            const int Tc = T - t0 < ch.Tc ? T - t0 : ch.Tc;
-            VjfFeWeightArgs wa{w_mean, w_chol, w_noise + ((size_t)ms0 * T + t0) * wstep, W, (size_t)T * wstep, Sc, Tc, n, dout};
-            const int64_t nq = (int64_t)Sc * Tc;
-            int64_t gy = (nq + VJF_FC_WAVES - 1) / VJF_FC_WAVES, cap = 2048 / mt;
-            if (gy > cap) gy = cap;
-            if (gy < 1) gy = 1;
-            hipLaunchKernelGGL(vjf_fe_weights_kernel, dim3(mt, (unsigned)gy), dim3(VJF_FC_THREADS), lds_w, s, wa);
-            VJF_HIP(hipGetLastError());
-            // row 0 of the chunk's states is x[t0] (the start, or the previous chunk's last row), rows 1 .. Tc are x[t0 + 1 ..]
-            float* rows = x_members ? x_members + (size_t)ms0 * xs_ms + (size_t)t0 * xstep : X;
-            VjfFeArgs e{};
-            VjfFcArgs& a = e.a;
-            if (t0 == 0) { a.x_in = x0 + (size_t)ms0 * x0_member_stride; e.x_in_ms = (size_t)x0_member_stride; a.x0_out = rows; e.x0_out_ms = xs_ms; }
-            else { a.x_in = x_members ? rows : X + (size_t)Tp * xstep; e.x_in_ms = xs_ms; a.x0_out = nullptr; }
-            a.u = u ? u + (size_t)t0 * B * du : nullptr;
-            a.e = s_noise ? s_noise + ((size_t)ms0 * T + t0) * xstep : nullptr; e.e_ms = (size_t)T * xstep;
-            a.c = centroid; a.logw = logwidth; a.W = W; e.W_ms = (size_t)Tc * wstep; a.tr_logvar = tr_logvar;
-            a.x_out = rows + xstep; e.x_out_ms = xs_ms;
-            a.Tc = Tc; a.B = B; a.n = n; a.d = d; a.dout = dout;
-            auto launch = [&](auto kernel) {
-                allow_lds(kernel, lds);
-                hipLaunchKernelGGL(kernel, dim3(tiles, Sc), dim3(VJF_FC_THREADS), lds, s, e);
-            };
-            if (la && dout <= 16) launch(vjf_fe_rollout_kernel<1, true>);
-            else if (la) launch(vjf_fe_rollout_kernel<2, true>);
-            else if (cl) launch(vjf_fe_rollout_kernel<0, true>);
-            else launch(vjf_fe_rollout_kernel<0, false>);
-            VJF_HIP(hipGetLastError());
-            if (t0 == 0) moments(rows, xs_ms, 0, Tc + 1, ms0, Sc);
-            else moments(rows + xstep, xs_ms, t0 + 1, Tc, ms0, Sc);
-            VJF_HIP(hipGetLastError());
-            Tp = Tc;
-        }
-    }
-    return 0;
+    const FcForms fm = fc_forms(n, d, dout);
+    if (!fm.fits) return fail(-11, "vjf_forecast_ens: n=%d, d=%d too large", n, d);
+    FeEns e{};
+    e.mf = fe_mom_forms(dout, dy); e.x0_ms = x0_member_stride; e.members = fc_env_int("VJF_FE_MEMBERS");
+    if (e.mf.lds > kMaxLds - 1024) return fail(-11, "vjf_forecast_ens: dout=%d too large", dout);
+    VjfFeMomArgs& m = e.mom;
+    m.dec_W = dec_W; m.dec_b = dec_b; m.x_mean = x_mean; m.x_var = x_var; m.y_mean = dy ? y_mean : nullptr; m.y_var = dy ? y_var : nullptr;
+    m.S = S; m.B = B; m.dout = dout; m.dy = dy; m.mb = e.mf.mb;
+    VjfFcArgs a{};
+    a.u = u; a.c = centroid; a.logw = logwidth; a.tr_logvar = tr_logvar; a.B = B; a.n = n; a.d = d; a.dout = dout;
+    return forecast_run(a, w_mean, w_chol, x0, w_noise, s_noise, x_members, scratch, T, fm, fc_env_int("VJF_FC_CHUNK"), &e, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {
@@ -867,28 +503,16 @@ int vjf_blr_rls(const float* x, const float* target, const float* v, float shrin
     if (!x || !target || !v || !centroid || !logwidth || !w_mean || !w_chol || !w_precision || !w_pchol || !scratch)
         return fail(-1, "vjf_blr_rls: null tensor");
     if (B < 1 || n < 1 || d < 1 || dout < 1) return fail(-20, "vjf_blr_rls: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    VjfPlan P; rls_plan(n, dout, &P);
-    const size_t lds = vjf_serial_lds_floats(P) * 4;
-    if (lds > kMaxLds - 1024) return fail(-11, "vjf_blr_rls: n=%d too large for the single-workgroup RLS kernel", n);
-    RlsCarve c{};
-    float* red = nullptr;
-    if (int rc = rls_statistics(P, scratch, x, centroid, logwidth, target, B, n, d, dout, s, &c, &red)) return rc;
-    char* ws = (char*)scratch;
-    allow_lds(vjf_rls_kernel, lds);
-    VjfRlsArgs a{};
-    a.Pm = w_precision; a.Wm = w_mean; a.Wc = w_chol; a.Lm = w_pchol;
-    a.G = red + P.red_G; a.FDX = red + P.red_FDX; a.v = v; a.work = (float*)(ws + c.work); a.status = status;
-    a.n = n; a.dout = dout; a.shrink = shrink;
-    hipLaunchKernelGGL(vjf_rls_kernel, dim3(1), dim3(VJF_K2_THREADS), lds, s, a);
-    VJF_HIP(hipGetLastError());
-    return 0;
+    return rls_update("vjf_blr_rls", "RLS kernel", vjf_rls_kernel, scratch, x, target, centroid, logwidth, B, n, d, dout, stream, [&](VjfRlsArgs& a, const RlsStats& st) {
+        a.Pm = w_precision; a.Wm = w_mean; a.Wc = w_chol; a.Lm = w_pchol;
+        a.G = st.red + st.P.red_G; a.FDX = st.red + st.P.red_FDX; a.v = v; a.work = (float*)(st.ws + st.c.work); a.status = status;
+        a.n = n; a.dout = dout; a.shrink = shrink;
+    });
 }
 
 int vjf_kalman_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {
     if (!bytes || B < 1 || n < 1 || dout < 1) return fail(-20, "vjf_kalman_scratch_size: bad argument");
-    const size_t nn = ((size_t)n * (n > dout ? n : dout) * 4 + 255) / 256 * 256;
-    *bytes = (int64_t)(rls_carve(B, n, dout, nullptr).total + 6 * nn);
+    *bytes = (int64_t)(rls_carve(B, n, dout, nullptr).total + 6 * kalman_stride(n, dout));
     return 0;
 }
 
@@ -898,52 +522,13 @@ int vjf_blr_kalman(const float* x, const float* target, const float* v, float di
     if (!x || !target || !v || !centroid || !logwidth || !w_mean || !w_chol || !scratch) return fail(-1, "vjf_blr_kalman: null tensor");
     if (B < 1 || n < 1 || d < 1 || dout < 1) return fail(-20, "vjf_blr_kalman: bad shape");
     if (!(diffusion >= 0.f)) return fail(-25, "vjf_blr_kalman: diffusion needs to be non-negative");   // module.py:127
-    hipStream_t s = (hipStream_t)stream;
-    VjfPlan P; rls_plan(n, dout, &P);
-    const size_t lds = vjf_serial_lds_floats(P) * 4;
-    if (lds > kMaxLds - 1024) return fail(-11, "vjf_blr_kalman: n=%d too large for the single-workgroup kernel", n);
-    RlsCarve c{};
-    float* red = nullptr;
-    if (int rc = rls_statistics(P, scratch, x, centroid, logwidth, target, B, n, d, dout, s, &c, &red)) return rc;
-    char* ws = (char*)scratch;
-    allow_lds(vjf_kalman_kernel, lds);
-    const size_t nn = ((size_t)n * (n > dout ? n : dout) * 4 + 255) / 256 * 256;
-    VjfKalmanArgs a{};
-    a.Wm = w_mean; a.Wc = w_chol; a.G = red + P.red_G; a.Fy = red + P.red_FDX; a.v = v;
-    for (int q = 0; q < 6; ++q) a.T[q] = (float*)(ws + c.total + (size_t)q * nn);
-    a.Dinv = (float*)(ws + c.work);
-    a.status = status; a.n = n; a.dout = dout; a.diffusion = diffusion;
-    hipLaunchKernelGGL(vjf_kalman_kernel, dim3(1), dim3(VJF_K2_THREADS), lds, s, a);
-    VJF_HIP(hipGetLastError());
-    return 0;
-}
-
-namespace {
-// vjf_recognition_forward(_act): act null or Tanh -> the Tanh kernel
-int recognition_forward(const char* who, const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
-                        const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
-                        float* lv_t, int32_t B, int32_t ydim, int32_t udim, int32_t xdim, int32_t n_hidden,
-                        const int32_t* hidden, const VjfAct* act, void* stream) {
-    if (!y || !mu_s || !lv_s || !rec_W || !rec_b || !mean_W || !lv_W || !lv_b || !mu_t || !lv_t || !hidden)
-        return fail(-1, "%s: null tensor", who);
-    if (udim > 0 && !u) return fail(-21, "%s: u is required when udim > 0", who);
-    if (n_hidden < 1 || n_hidden > VJF_MAX_HIDDEN) return fail(-3, "%s: n_hidden=%d", who, n_hidden);
-    if (B < 1) return fail(-20, "%s: bad shape", who);
-    VjfRecArgs a{};
-    a.y = y; a.u = u; a.mu_s = mu_s; a.lv_s = lv_s; a.mean_W = mean_W; a.lv_W = lv_W; a.lv_b = lv_b; a.mu_t = mu_t; a.lv_t = lv_t;
-    a.B = B; a.dy = ydim; a.du = udim; a.dz = xdim; a.L = n_hidden;
-    int hmax = 0;
-    for (int l = 0; l < n_hidden; ++l) { a.W[l] = rec_W[l]; a.b[l] = rec_b[l]; a.h[l] = hidden[l]; if (hidden[l] > hmax) hmax = hidden[l]; }
-    const size_t lds = (size_t)VJF_LDT * (ydim + udim + 2 * xdim + 2 * hmax) * 4;
-    if (lds > kMaxLds - 1024) return fail(-10, "%s: layer widths do not fit LDS", who);
-    with_act_kernel(act ? *act : VjfAct{VJF_ACT_TANH, 0.f, 0.f}, vjf_recognition_kernel, vjf_recognition_act_kernel, [&](auto kernel, auto... tail) {
-        allow_lds(kernel, lds);
-        hipLaunchKernelGGL(kernel, dim3((B + 15) / 16), dim3(VJF_K1_THREADS), lds, (hipStream_t)stream, a, hmax, tail...);
+    return rls_update("vjf_blr_kalman", "kernel", vjf_kalman_kernel, scratch, x, target, centroid, logwidth, B, n, d, dout, stream, [&](VjfKalmanArgs& a, const RlsStats& st) {
+        a.Wm = w_mean; a.Wc = w_chol; a.G = st.red + st.P.red_G; a.Fy = st.red + st.P.red_FDX; a.v = v;
+        for (int q = 0; q < 6; ++q) a.T[q] = (float*)(st.ws + st.c.total + (size_t)q * kalman_stride(n, dout));
+        a.Dinv = (float*)(st.ws + st.c.work);
+        a.status = status; a.n = n; a.dout = dout; a.diffusion = diffusion;
     });
-    VJF_HIP(hipGetLastError());
-    return 0;
 }
-}  // namespace
 
 int vjf_recognition_forward(const float* y, const float* u, const float* mu_s, const float* lv_s, const float* const* rec_W,
                             const float* const* rec_b, const float* mean_W, const float* lv_W, const float* lv_b, float* mu_t,
@@ -967,27 +552,19 @@ int vjf_gaussian_loss(const float* m1, const float* lv1, const float* m2, const 
                       int32_t B, int32_t d, void* stream) {
     if (!m1 || !m2 || !logvar || !out) return fail(-1, "vjf_gaussian_loss: null tensor");
     if (B < 1 || d < 1) return fail(-20, "vjf_gaussian_loss: bad shape");
-    hipLaunchKernelGGL(vjf_loss_kernel, dim3(VJF_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, 0, m1, lv1, m2, lv2, logvar, out, B, d, loss_slot());
-    VJF_HIP(hipGetLastError());
-    return 0;
+    return launch_loss(0, m1, lv1, m2, lv2, logvar, out, B, d, (hipStream_t)stream);
 }
 
 int vjf_gaussian_entropy(const float* lv, float* out, int32_t B, int32_t d, void* stream) {
     if (!lv || !out) return fail(-1, "vjf_gaussian_entropy: null tensor");
     if (B < 1 || d < 1) return fail(-20, "vjf_gaussian_entropy: bad shape");
-    hipLaunchKernelGGL(vjf_loss_kernel, dim3(VJF_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, 1, lv, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, out, B, d, loss_slot());
-    VJF_HIP(hipGetLastError());
-    return 0;
+    return launch_loss(1, lv, nullptr, nullptr, nullptr, nullptr, out, B, d, (hipStream_t)stream);
 }
 
 int vjf_poisson_loss(const float* eta, const float* target, float* out, int32_t B, int32_t d, void* stream) {
     if (!eta || !target || !out) return fail(-1, "vjf_poisson_loss: null tensor");
     if (B < 1 || d < 1) return fail(-20, "vjf_poisson_loss: bad shape");
-    hipLaunchKernelGGL(vjf_loss_kernel, dim3(VJF_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, 2, eta, (const float*)nullptr, target,
-                       (const float*)nullptr, (const float*)nullptr, out, B, d, loss_slot());
-    VJF_HIP(hipGetLastError());
-    return 0;
+    return launch_loss(2, eta, nullptr, target, nullptr, nullptr, out, B, d, (hipStream_t)stream);
 }
 
 int vjf_linear_forward(const float* x, const float* W, const float* b, float* out, int32_t B, int32_t din, int32_t dout, void* stream) {

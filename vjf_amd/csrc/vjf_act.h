@@ -1,7 +1,7 @@
 // vjf_act.h -- the activations of the recognition layers (vjf/recognition.py:17-24: `activation` is any module class; the
 // reference default is Tanh).  One definition, shared by every route: the one-launch trial role (vjf_mega_kernel.h), the
 // per-step matrix-core trial kernel (vjf_trial_mfma_kernel.h), the wide route's element-wise pass (vjf_trial_wide.h) and the
-// stand-alone operator (vjf_abi.hip).
+// stand-alone operator (vjf_recognition_kernel.h).
 //
 // The supported set is the activations whose derivative follows from the layer's OUTPUT h: every route keeps h (LDS, the ACT
 // columns of the workspace) and never the pre-activation a.  Each derivative is the one torch's autograd uses for that module

@@ -9,11 +9,12 @@
 //
 // Tiling as in vjf_forecast_kernel.h: activations feature-major in LDS ([feature][VJF_LDT]), the trial on the MFMA column of
 // v_mfma_f32_16x16x4_f32.  Workgroups are independent: no cooperative launch, no hand-off, no atomics.
-// Included from vjf_abi.hip behind vjf_forecast_kernel.h.
+// Included by vjf_host_forecast.h.  The kernels sit in an anonymous namespace: their symbols carry it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_forecast_kernel.h"     // VjfFcArgs, fc_k_range, VJF_FC_*
 
+namespace {
 struct VjfFeWeightArgs {
     const float* w_mean; const float* w_chol;
     const float* noise;        // member sl, step t of the chunk at noise + sl * noise_ms + t * n * dout
@@ -210,3 +211,4 @@ __global__ __launch_bounds__(VJF_FE_THREADS) void vjf_fe_moments_kernel(VjfFeMom
         }
     }
 }
+}  // namespace

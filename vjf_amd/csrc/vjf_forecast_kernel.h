@@ -7,7 +7,7 @@
 //
 // Both follow vjf_blr_predict_kernel's tiling: activations feature-major in LDS ([feature][VJF_LDT]), products as 16 x 16 tiles on
 // v_mfma_f32_16x16x4_f32 with the trial on the MFMA column.  Workgroups are independent: no cooperative launch, no hand-off.
-// Included from vjf_abi.hip behind vjf_blr_predict_kernel (mma_tile, VJF_LDT, VJF_K1_THREADS).
+// Included by vjf_host_forecast.h.  The kernels sit in an anonymous namespace: their symbols carry it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_trial_mfma_kernel.h"   // mma_tile, vjf_f32x4, VJF_LDT
@@ -16,6 +16,7 @@
 #define VJF_FC_WAVES (VJF_FC_THREADS / 64)
 #define VJF_FC_KQ 16                 // MFMA steps of one wavefront's share of K that the look-ahead keeps in registers (n <= 256)
 
+namespace {
 struct VjfFcWeightArgs {
     const float* w_mean; const float* w_chol; const float* noise;   // (n, dout), (n, n) dense, (Tc, n, dout)
     float* W;                                                       // (Tc, n, dout)
@@ -77,3 +78,4 @@ template <int NT, bool CL>
 __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fc_rollout_kernel(VjfFcArgs A) {
 #include "vjf_fc_rollout_body.h"        // the step loop on `A` (shared with vjf_fe_rollout_kernel)
 }
+}  // namespace

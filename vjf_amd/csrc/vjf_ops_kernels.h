@@ -2,6 +2,8 @@
 // These serve the reference's operator API one call at a time; the fused step does not use them.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vjf_trial_kernel.h"        // VJF_K1_THREADS
+#include "vjf_trial_mfma_kernel.h"   // mma_tile, vjf_f32x4, VJF_LDT
 
 // functional.rbf (vjf/functional.py:11-22): workgroup = 256 centroids x 16 trials.  A thread runs ITS centroid (its own row, read
 // 8 coordinates at a time) against the 16 trials staged in LDS (same address on every lane: broadcast reads, 16 bytes at a
@@ -106,3 +108,89 @@ __global__ __launch_bounds__(256) void vjf_loss_kernel(int mode, const float* m1
 __global__ void vjf_scale_kernel(float* p, float f, int n) {
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) p[e] *= f;
 }
+
+namespace {   // (internal linkage from here on, as the forecast and recognition kernels have: their symbols carry it)
+struct VjfPredArgs {
+    const float* x; const float* c; const float* logw; const float* w_mean; const float* w_chol;
+    float* mean; float* logvar; int B, n, d, dout;
+};
+// 16 trials per workgroup: features feature-major in LDS ([feature][17], as the fused kernels hold them), then Phi W (mean)
+// and the row norm of Phi w_chol (logvar) as 16 x 16 output tiles on v_mfma_f32_16x16x4_f32 (mma_tile: the matrices are k-major
+// for these products), one tile per wavefront and round.
+__global__ __launch_bounds__(VJF_K1_THREADS) void vjf_blr_predict_kernel(VjfPredArgs A) {
+    constexpr int TB = 16, LD = VJF_LDT, NW = VJF_K1_THREADS / 64;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_phi = smem;                 // n x LD
+    float* s_red = s_phi + A.n * LD;     // NW x TB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b0 = blockIdx.x * TB, nb = min(TB, A.B - b0);
+    for (int i = tid; i < TB * A.n; i += VJF_K1_THREADS) {
+        const int k = i / TB, b = i - k * TB;
+        float ph = 0.f;
+        if (b < nb) {
+            float d2 = 0.f;
+            for (int j = 0; j < A.d; ++j) { const float t = A.x[(size_t)(b0 + b) * A.d + j] - A.c[(size_t)k * A.d + j]; d2 = fmaf(t, t, d2); }
+            const float w = expf(A.logw[k]);
+            ph = expf(-0.5f * d2 / (w * w));
+        }
+        s_phi[k * LD + b] = ph;
+    }
+    __syncthreads();
+    const int col = lane & 15, r4 = 4 * (lane >> 4);     // accumulator: row = r4 + r (output), column = trial
+    if (A.mean)
+        for (int t = wave; t * 16 < A.dout; t += NW) {
+            vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            mma_tile(acc, A.w_mean, A.dout, A.dout, t * 16, s_phi, A.n, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = t * 16 + r4 + r;
+                if (j < A.dout && col < nb) A.mean[(size_t)(b0 + col) * A.dout + j] = acc[r];
+            }
+        }
+    if (!A.logvar) return;
+    float v2 = 0.f;                                      // this lane's share of sum_j Z[trial col][j]^2
+    for (int t = wave; t * 16 < A.n; t += NW) {
+        vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        mma_tile(acc, A.w_chol, A.n, A.n, t * 16, s_phi, A.n, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v2 = fmaf(acc[r], acc[r], v2);      // (rows beyond n are exact zeros)
+    }
+    v2 += __shfl_xor(v2, 16, 64);                        // the four row groups of a column, fixed order
+    v2 += __shfl_xor(v2, 32, 64);
+    if (lane < 16) s_red[wave * TB + lane] = v2;
+    __syncthreads();
+    for (int i = tid; i < nb * A.dout; i += VJF_K1_THREADS) {
+        const int b = i / A.dout;
+        float v = s_red[b];
+        for (int w = 1; w < NW; ++w) v += s_red[w * TB + b];
+        A.logvar[(size_t)(b0 + b) * A.dout + (i - b * A.dout)] = logf(v);
+    }
+}
+
+// features + target rows of the stand-alone RLS:  E[b] = [Phi(x_b) | target_b | 0]
+__global__ void vjf_rls_rows_kernel(const float* x, const float* c, const float* logw, const float* target, float* E,
+                                    int B, int n, int d, int dout, int ldE) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * ldE) return;
+    const int b = (int)(i / ldE), k = (int)(i - (size_t)b * ldE);
+    float v = 0.f;
+    if (k < n) {
+        float d2 = 0.f;
+        for (int j = 0; j < d; ++j) { const float t = x[(size_t)b * d + j] - c[(size_t)k * d + j]; d2 = fmaf(t, t, d2); }
+        const float w = expf(logw[k]);
+        v = expf(-0.5f * d2 / (w * w));
+    } else if (k < n + dout) {
+        v = target[(size_t)b * dout + (k - n)];
+    }
+    E[i] = v;
+}
+
+}  // namespace
+
+// Recognition.forward for 16 trials per workgroup: activations feature-major in LDS (ping-pong), every layer as 16 x 16 output
+// tiles on v_mfma_f32_16x16x4_f32 with the weights read as torch stores them (mma_tile<true>).
+#define VJF_RECOGNITION_ACT 0
+#include "vjf_recognition_kernel.h"     // vjf_recognition_kernel
+#undef VJF_RECOGNITION_ACT
+#define VJF_RECOGNITION_ACT 1
+#include "vjf_recognition_kernel.h"     // vjf_recognition_act_kernel
+#undef VJF_RECOGNITION_ACT

@@ -1,7 +1,19 @@
-// vjf_recognition_kernel.h -- the stand-alone Recognition.forward kernel (vjf_abi.hip: vjf_recognition_forward(_act)), included twice
-// from there, inside its anonymous namespace (VjfRecArgs):
+// vjf_recognition_kernel.h -- the stand-alone Recognition.forward kernel (vjf_host_ops.h: recognition_forward), included twice from
+// vjf_ops_kernels.h behind mma_tile, VJF_LDT, VJF_K1_THREADS and vjf_act.h:
 //   VJF_RECOGNITION_ACT 0: vjf_recognition_kernel (tanh);  1: vjf_recognition_act_kernel (the activation `act`, vjf_act.h).
-// (two textual instantiations, as vjf_trial_mfma_body.h: the Tanh kernel's code stays what it was; no include guard)
+// (two textual instantiations, as vjf_trial_mfma_body.h: the Tanh kernel's code stays what it was; no include guard but the
+//  argument struct's.  Both kernels in an anonymous namespace: their symbols carry it.)
+namespace {
+#ifndef VJF_REC_ARGS_DEFINED
+#define VJF_REC_ARGS_DEFINED
+struct VjfRecArgs {
+    const float* y; const float* u; const float* mu_s; const float* lv_s;
+    const float* W[VJF_MAX_HIDDEN]; const float* b[VJF_MAX_HIDDEN];
+    const float* mean_W; const float* lv_W; const float* lv_b;
+    float* mu_t; float* lv_t;
+    int B, dy, du, dz, L; int h[VJF_MAX_HIDDEN];
+};
+#endif
 #if VJF_RECOGNITION_ACT
 __global__ __launch_bounds__(VJF_K1_THREADS) void vjf_recognition_act_kernel(VjfRecArgs A, int hmax, VjfAct act) {
 #else
@@ -66,4 +78,4 @@ __global__ __launch_bounds__(VJF_K1_THREADS) void vjf_recognition_kernel(VjfRecA
         }
     }
 }
-
+}  // namespace

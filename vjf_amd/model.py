@@ -18,6 +18,7 @@ import atexit
 import os
 import ctypes
 import logging
+import math
 import sys
 import weakref
 from collections import namedtuple
@@ -35,7 +36,7 @@ from .functional import gaussian_loss
 from .likelihood import GaussianLikelihood, PoissonLikelihood
 from .module import RBF, LinearRegression, rebind
 from .recognition import Recognition
-from .util import dev32, nonecat, reparametrize, running_var, storage_device, stream_ptr
+from .util import dev32, kept_scratch, nonecat, reparametrize, running_var, storage_device, stream_ptr
 
 try:                                   # progress bar as in the reference (vjf/model.py:245)
     from tqdm import trange
@@ -202,6 +203,60 @@ class RBFDS(Module):
         o = self._owner() if self._owner is not None else None
         return o.noise if o is not None else "reference"
 
+    def _forecast_inputs(self, x0, u, lead, noise, w_noise, state_noise):
+        """(u, w_noise, state_noise, held) as vjf_forecast_seq / vjf_forecast_ens take them: given ones coerced, missing ones drawn.
+        `lead`: the noise tensors' leading shape, (T,) for one roll-out, (S, T) for an ensemble; x0: (..., B, xdim) on its device.
+        `held`: the per-step host draws, which the caller keeps until its native call is enqueued: a few hundred small tensors are
+        then released while the device works, not in front of the launch."""
+        vel = self.velocity
+        B, dout = x0.shape[-2:]
+        n, d = vel.feature.centroid.shape
+        du, T = d - dout, lead[-1]
+        if du > 0:
+            if u is None:
+                raise TypeError("u is required when udim > 0")
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == T, 'u must have length of n_step if present'
+            if u.ndim == 2 and B == 1:
+                u = u[:, None, :]
+            assert u.shape == (T, B, du)
+            u = u.contiguous()
+        else:
+            u = None
+        if w_noise is not None:
+            w_noise = dev32(w_noise, ndim2=False)
+            assert w_noise.shape == (*lead, n, dout)
+        if state_noise is not None:
+            state_noise = dev32(state_noise, ndim2=False)
+            if state_noise.ndim == len(lead) + 1 and B == 1:
+                state_noise = state_noise.unsqueeze(-2)
+            assert state_noise.shape == (*lead, B, dout)
+            state_noise = state_noise.contiguous()
+        want_w, want_s = w_noise is None and T > 0, state_noise is None and noise and T > 0
+        ws = []
+        if self._noise_mode() != "reference":
+            if want_w:
+                w_noise = torch.randn(*lead, n, dout, device=x0.device, dtype=torch.float32)
+            if want_s:
+                state_noise = torch.randn(*lead, B, dout, device=x0.device, dtype=torch.float32)
+        elif want_w or want_s:
+            # forecast's order, roll-out by roll-out: per step the weight draw, then the state draw.  (The state draws go straight into
+            # one page-locked tensor, a contiguous slice per step -- the values and the generator state of `randn(B, xdim)` -- and from
+            # there to the device in one copy: at 4096 trials the draws themselves are most of the call's time, a stack of 200 tensors
+            # and a pageable copy would add half as much again)
+            dt, steps = torch.get_default_dtype(), math.prod(lead)
+            ss = torch.empty(steps, B, dout, dtype=dt, pin_memory=x0.is_cuda) if want_s else None
+            for i in range(steps):
+                if want_w:
+                    ws.append(vel._draw_weight_noise())
+                if want_s:
+                    torch.randn(B, dout, dtype=dt, out=ss[i])
+            if want_w:
+                w_noise = dev32(torch.stack(ws).reshape(*lead, n, dout), ndim2=False)
+            if want_s:
+                state_noise = ss.to(x0.device, torch.float32, non_blocking=True).contiguous().view(*lead, B, dout)
+        return u, w_noise, state_noise, ws
+
     def forecast_sequence(self, x0: Tensor, u: Tensor = None, n_step: int = 1, *, noise: bool = False,
                           w_noise: Tensor = None, state_noise: Tensor = None) -> Tensor:
         """`forecast` as ONE C-ABI call (vjf_forecast_seq): the weight samples of all steps from one batched product, then the
@@ -217,59 +272,14 @@ class RBFDS(Module):
         vel = self.velocity
         B, dout = x0.shape
         n, d = vel.feature.centroid.shape
-        du = d - dout
         assert dout == vel.n_output, f"x0 has {dout} columns, expected xdim={vel.n_output}"
         T = int(n_step)
         assert T >= 0, 'n_step must not be negative'
-        if du > 0:
-            if u is None:
-                raise TypeError("u is required when udim > 0")
-            u = dev32(u, ndim2=False)
-            assert u.shape[0] == T, 'u must have length of n_step if present'
-            if u.ndim == 2 and B == 1:
-                u = u[:, None, :]
-            assert u.shape == (T, B, du)
-            u = u.contiguous()
-        else:
-            u = None
-        if w_noise is not None:
-            w_noise = dev32(w_noise, ndim2=False)
-            assert w_noise.shape == (T, n, dout)
-        if state_noise is not None:
-            state_noise = dev32(state_noise, ndim2=False)
-            if state_noise.ndim == 2 and B == 1:
-                state_noise = state_noise[:, None, :]
-            assert state_noise.shape == (T, B, dout)
-            state_noise = state_noise.contiguous()
+        u, w_noise, state_noise, _held = self._forecast_inputs(x0, u, (T,), noise, w_noise, state_noise)   # (_held: freed after the launch)
         if T == 0:
             return x0[None].clone()
-        want_w, want_s = w_noise is None, state_noise is None and noise
-        if want_w or want_s:
-            if self._noise_mode() == "reference":          # forecast's order: per step the weight draw, then the state draw
-                # (the state draws go straight into one page-locked tensor, a contiguous slice per step -- the values and the generator
-                #  state of `randn(B, xdim)` -- and from there to the device in one copy: at 4096 trials the draws themselves are most of
-                #  the call's time, a stack of 200 tensors and a pageable copy would add half as much again)
-                dt, ws = torch.get_default_dtype(), []
-                ss = torch.empty(T, B, dout, dtype=dt, pin_memory=x0.is_cuda) if want_s else None
-                for t in range(T):
-                    if want_w:
-                        ws.append(vel._draw_weight_noise())
-                    if want_s:
-                        torch.randn(B, dout, dtype=dt, out=ss[t])
-                if want_w:
-                    w_noise = dev32(torch.stack(ws), ndim2=False)
-                if want_s:
-                    state_noise = ss.to(x0.device, torch.float32, non_blocking=True).contiguous()
-            else:
-                if want_w:
-                    w_noise = torch.randn(T, n, dout, device=x0.device, dtype=torch.float32)
-                if want_s:
-                    state_noise = torch.randn(T, B, dout, device=x0.device, dtype=torch.float32)
         L = N.lib()
-        nbytes = ctypes.c_int64()
-        N.check(L.vjf_forecast_scratch_size(T, n, dout, ctypes.byref(nbytes)), "vjf_forecast_scratch_size")
-        if self._fc_scratch is None or self._fc_scratch.numel() < nbytes.value or self._fc_scratch.device != x0.device:   # (kept, grown on demand)
-            self._fc_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x0.device)
+        self._fc_scratch = kept_scratch(self._fc_scratch, x0.device, L.vjf_forecast_scratch_size, T, n, dout)
         x = torch.empty(T + 1, B, dout, device=x0.device, dtype=torch.float32)
         N.check(L.vjf_forecast_seq(N.ptr(x0), N.ptr(u), N.ptr(w_noise), N.ptr(state_noise), N.ptr(vel.feature.centroid),
                                    N.ptr(vel.feature.logwidth), N.ptr(vel.w_mean), N.ptr(vel.w_chol), N.ptr(self.logvar), N.ptr(x),
@@ -330,53 +340,10 @@ class RBFDS(Module):
         B, dout = x0.shape[-2:]
         per_member = x0.ndim == 3
         assert x0.ndim == 2 or x0.shape[0] == S, f"x0 has {x0.shape[0]} starts, expected n_sample={S}"
-        du = d - dout
         assert dout == vel.n_output, f"x0 has {dout} columns, expected xdim={vel.n_output}"
-        if du > 0:
-            if u is None:
-                raise TypeError("u is required when udim > 0")
-            u = dev32(u, ndim2=False)
-            assert u.shape[0] == T, 'u must have length of n_step if present'
-            if u.ndim == 2 and B == 1:
-                u = u[:, None, :]
-            assert u.shape == (T, B, du)
-            u = u.contiguous()
-        else:
-            u = None
-        if w_noise is not None:
-            w_noise = dev32(w_noise, ndim2=False)
-            assert w_noise.shape == (S, T, n, dout)
-        if state_noise is not None:
-            state_noise = dev32(state_noise, ndim2=False)
-            if state_noise.ndim == 3 and B == 1:
-                state_noise = state_noise[:, :, None, :]
-            assert state_noise.shape == (S, T, B, dout)
-            state_noise = state_noise.contiguous()
-        want_w, want_s = w_noise is None and T > 0, state_noise is None and noise and T > 0
-        if want_w or want_s:
-            if reference:                                  # member by member, forecast's order within each (see forecast_sequence)
-                ws = []
-                ss = torch.empty(S, T, B, dout, dtype=dt, pin_memory=x0.is_cuda) if want_s else None
-                for m in range(S):
-                    for t in range(T):
-                        if want_w:
-                            ws.append(vel._draw_weight_noise())
-                        if want_s:
-                            torch.randn(B, dout, dtype=dt, out=ss[m, t])
-                if want_w:
-                    w_noise = dev32(torch.stack(ws).reshape(S, T, n, dout), ndim2=False)
-                if want_s:
-                    state_noise = ss.to(x0.device, torch.float32, non_blocking=True).contiguous()
-            else:
-                if want_w:
-                    w_noise = torch.randn(S, T, n, dout, device=x0.device, dtype=torch.float32)
-                if want_s:
-                    state_noise = torch.randn(S, T, B, dout, device=x0.device, dtype=torch.float32)
+        u, w_noise, state_noise, _held = self._forecast_inputs(x0, u, (S, T), noise, w_noise, state_noise)   # (_held: freed after the launch)
         L = N.lib()
-        nbytes = ctypes.c_int64()
-        N.check(L.vjf_forecast_ens_scratch_size(T, S, B, n, dout, ctypes.byref(nbytes)), "vjf_forecast_ens_scratch_size")
-        if self._fe_scratch is None or self._fe_scratch.numel() < nbytes.value or self._fe_scratch.device != x0.device:   # (kept, grown on demand)
-            self._fe_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x0.device)
+        self._fe_scratch = kept_scratch(self._fe_scratch, x0.device, L.vjf_forecast_ens_scratch_size, T, S, B, n, dout)
         new = lambda *shape: torch.empty(*shape, device=x0.device, dtype=torch.float32)      # noqa: E731
         x_mean, x_var = new(T + 1, B, dout), new(T + 1, B, dout)
         W = b = y_mean = y_var = None

@@ -15,7 +15,7 @@ from torch.nn import Module, Parameter
 
 from . import _native as N
 from .distribution import Gaussian
-from .util import dev32, stream_ptr
+from .util import dev32, kept_scratch, stream_ptr
 
 
 def _to_dev(t: Tensor) -> Tensor:
@@ -121,11 +121,7 @@ class LinearRegression(Module):
         B, n, d, dout = self._dims(x)
         assert target.shape == (B, dout)
         L = N.lib()
-        import ctypes
-        nbytes = ctypes.c_int64()
-        N.check(L.vjf_rls_scratch_size(B, n, dout, ctypes.byref(nbytes)), "vjf_rls_scratch_size")
-        if self._rls_scratch is None or self._rls_scratch.numel() < nbytes.value:
-            self._rls_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+        self._rls_scratch = kept_scratch(self._rls_scratch, x.device, L.vjf_rls_scratch_size, B, n, dout)
         vt = dev32(v, ndim2=False).reshape(1)
         status = torch.zeros(1, dtype=torch.int32, device=x.device)
         N.check(L.vjf_blr_rls(N.ptr(x), N.ptr(target), N.ptr(vt), float(shrink), N.ptr(self.feature.centroid),
@@ -147,11 +143,7 @@ class LinearRegression(Module):
         B, n, d, dout = self._dims(x)
         assert target.shape == (B, dout)
         L = N.lib()
-        import ctypes
-        nbytes = ctypes.c_int64()
-        N.check(L.vjf_kalman_scratch_size(B, n, dout, ctypes.byref(nbytes)), "vjf_kalman_scratch_size")
-        if self._rls_scratch is None or self._rls_scratch.numel() < nbytes.value:
-            self._rls_scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+        self._rls_scratch = kept_scratch(self._rls_scratch, x.device, L.vjf_kalman_scratch_size, B, n, dout)
         vt = dev32(v, ndim2=False).reshape(1)
         status = torch.zeros(1, dtype=torch.int32, device=x.device)
         N.check(L.vjf_blr_kalman(N.ptr(x), N.ptr(target), N.ptr(vt), float(diffusion), N.ptr(self.feature.centroid),

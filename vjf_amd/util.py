@@ -1,9 +1,11 @@
 """Host-side helpers mirroring vjf/util.py, plus device plumbing shared by the operator shims."""
+import ctypes
 from typing import Tuple, Union
 
 import torch
 from torch import Tensor
 
+from . import _native as N
 from .distribution import Gaussian
 
 
@@ -37,12 +39,21 @@ def dev32(a, ndim2: bool = True) -> Tensor:
     return t.contiguous()
 
 
+def kept_scratch(kept: Tensor, dev: torch.device, size_fn, *dims) -> Tensor:
+    """The scratch tensor a module keeps between calls: `kept` while it has the bytes `size_fn(*dims, &bytes)` of the library asks
+    for on `dev`, else a fresh one (absent, too small, or left behind on another device)."""
+    nbytes = ctypes.c_int64()
+    N.check(size_fn(*dims, ctypes.byref(nbytes)), size_fn.__name__)
+    if kept is None or kept.numel() < nbytes.value or kept.device != dev:
+        kept = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    return kept
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def stream_ptr():
     """The HIP stream torch is on (the library launches on the caller's stream): the raw handle, without a Stream object."""
-    import ctypes
     if not torch.cuda.is_available():
         return ctypes.c_void_p(0)
     if _raw_stream is not None:
