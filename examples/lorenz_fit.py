@@ -2,10 +2,11 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--plot out.png]
 
 With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
-the +-2 sd band of the first latent at a few steps.
+the +-2 sd band of the first latent at a few steps.  With --lyapunov N it prints the Lyapunov spectrum of the learned flow over N steps
+from the last posterior mean (`lyapunov`) and the moduli of the Jacobian's eigenvalues there (`jacobian`).
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -28,6 +29,7 @@ def main(argv=None):
     ap.add_argument("--n-rbf", type=int, default=100)
     ap.add_argument("--forecast", type=int, default=200)
     ap.add_argument("--ensemble", type=int, default=0, help="members of the forecast with uncertainty (0: skip it), e.g. 64")
+    ap.add_argument("--lyapunov", type=int, default=0, help="steps of the Lyapunov spectrum of the learned flow (0: skip it), e.g. 10000")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -54,6 +56,14 @@ def main(argv=None):
         mean, sd = fe.x_mean[:, 0, 0].cpu(), fe.x_var[:, 0, 0].sqrt().cpu()
         for t in sorted({0, a.forecast // 4, a.forecast // 2, a.forecast}):
             print(f"ensemble forecast: step {t:4d}  x1 = {float(mean[t]):+.3f}  [{float(mean[t] - 2 * sd[t]):+.3f}, {float(mean[t] + 2 * sd[t]):+.3f}]")
+    if a.lyapunov > 0:
+        # the geometry of the learned flow: its Lyapunov spectrum from the last posterior mean, the whole horizon in one native call
+        # (per step of the model; in Gram-Schmidt column order, which a long horizon sorts), and the Jacobian's eigenvalues there
+        ly = model.lyapunov(q_last, n_step=a.lyapunov, burn_in=min(1000, a.lyapunov))
+        print(f"lyapunov: {a.lyapunov} steps  exponents per step = {[round(float(v), 5) for v in ly.exponents[0].cpu()]}"
+              f"  sum = {float(ly.exponents[0].sum()):+.5f}")
+        ev = torch.linalg.eigvals(model.jacobian(q_last)[0].cpu())
+        print("jacobian at the last posterior mean: |eigenvalues| =", [round(float(v), 4) for v in ev.abs()])
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

@@ -293,6 +293,27 @@ int vjf_forecast_ens(const float* x0, int64_t x0_member_stride, const float* u, 
                      const float* tr_logvar, const float* dec_W, const float* dec_b, float* x_mean, float* x_var,
                      float* y_mean, float* y_var, float* x_members, void* scratch, int32_t T, int32_t S, int32_t B,
                      int32_t n, int32_t d, int32_t dout, int32_t dy, void* stream);
+/* Tangent dynamics of the mean map of RBFDS.forward(sampling=False) (vjf/model.py:334-340 over vjf/module.py:64-77),
+ *   f(x, u) = x + Phi([x, u]) w_mean,   J(x, u) = df/dx = I - w_mean^T G,   G[k][j] = phi_k (x_j - c_kj) / exp(logwidth_k)^2,
+ * as one call: T steps of x[t+1] = f(x[t], u[t]), Q <- J(x[t], u[t]) Q for a frame Q (dout x m per trial), and every qr_every steps
+ * (and behind the last step) one pass of modified Gram-Schmidt in column order on every trial's frame, fp32, R_vv > 0, log R_vv added
+ * to lsum[b][v] in interval order and stored to lhist[interval][b][v] if given.  lsum / (T dt) are the m leading Lyapunov exponents
+ * in Gram-Schmidt column order.  qr_every = 0: the frame is never normalised and q_out is the raw product -- one step from Q = I with
+ * m = dout is J itself, q_out[b][i][j] = df_i/dx_j (lsum may be NULL, lhist must be).
+ * x0 (B,dout); u (T,B,du) or NULL (du = d - dout); q0 (B,dout,m) or NULL: the first m columns of I; x_out (B,dout), q_out (B,dout,m):
+ * the final state and frame, from which a further call continues the run bit for bit when the cut is at an interval boundary; lsum
+ * (B,m) in/out (accumulate = 0: the sums start from 0 and lsum is only written); lhist (ceil(T / qr_every),B,m) or NULL.
+ * T = 0: x_out = x0, q0 is orthonormalised once and its log R_vv are added (qr_every > 0).  A trial's outputs depend on that trial's
+ * inputs alone, bit for bit.  Asynchronous on `stream`, no host synchronisation, no scratch; reads the state tensors, writes none.
+ * Steps run in launches of at most 4096 (VJF_FC_CHUNK: fewer), the state carried through the output buffers.
+ * -1 null tensor, -20 bad shape (also m < 1, m > dout, qr_every < 0, lhist with qr_every = 0), -21 u missing with d > dout, -11 the
+ * shape is beyond one workgroup's LDS or dout > 64: all before the first launch.
+ * vjf_tangent_plan: what the call takes for these sizes -- tangent vectors per pass over the features (m wherever it fits; the
+ * results do not depend on it) and the dynamic LDS of a workgroup; -11 / -20 as the call. */
+int vjf_tangent_plan(int32_t n, int32_t d, int32_t dout, int32_t m, int32_t* vectors_per_pass, int64_t* lds_bytes);
+int vjf_tangent_rollout(const float* x0, const float* u, const float* q0, const float* centroid, const float* logwidth,
+                        const float* w_mean, float* x_out, float* q_out, float* lsum, float* lhist, int32_t T, int32_t B,
+                        int32_t n, int32_t d, int32_t dout, int32_t m, int32_t qr_every, int32_t accumulate, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

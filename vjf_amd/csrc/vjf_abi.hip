@@ -37,6 +37,7 @@
 #include "vjf_host_routes.h"
 #include "vjf_host_ops.h"
 #include "vjf_host_forecast.h"
+#include "vjf_host_tangent.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -489,6 +490,31 @@ int vjf_forecast_ens(const float* x0, int64_t x0_member_stride, const float* u, 
     VjfFcArgs a{};
     a.u = u; a.c = centroid; a.logw = logwidth; a.tr_logvar = tr_logvar; a.B = B; a.n = n; a.d = d; a.dout = dout;
     return forecast_run(a, w_mean, w_chol, x0, w_noise, s_noise, x_members, scratch, T, fm, fc_env_int("VJF_FC_CHUNK"), &e, (hipStream_t)stream);
+}
+
+int vjf_tangent_plan(int32_t n, int32_t d, int32_t dout, int32_t m, int32_t* vectors_per_pass, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout || m < 1 || m > dout) return fail(-20, "vjf_tangent_plan: bad shape (n=%d d=%d dout=%d m=%d)", n, d, dout, m);
+    const TgPlan p = tg_plan(n, d, dout, m, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_FC_LOOKAHEAD"));
+    if (!p.fits) return fail(-11, "vjf_tangent_plan: n=%d, d=%d, dout=%d, m=%d beyond one workgroup's LDS", n, d, dout, m);
+    if (vectors_per_pass) *vectors_per_pass = p.vg;
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_tangent_rollout(const float* x0, const float* u, const float* q0, const float* centroid, const float* logwidth, const float* w_mean,
+                        float* x_out, float* q_out, float* lsum, float* lhist, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout,
+                        int32_t m, int32_t qr_every, int32_t accumulate, void* stream) {
+    if (!x0 || !centroid || !logwidth || !w_mean || !x_out || !q_out || (qr_every > 0 && !lsum)) return fail(-1, "vjf_tangent_rollout: null tensor");
+    if (T < 0 || B < 1 || n < 1 || dout < 1 || d < dout || m < 1 || m > dout || qr_every < 0 || (qr_every == 0 && lhist))
+        return fail(-20, "vjf_tangent_rollout: bad shape (T=%d B=%d n=%d d=%d dout=%d m=%d qr_every=%d%s)", T, B, n, d, dout, m, qr_every,
+                    qr_every == 0 && lhist ? ", a history without intervals" : "");
+    if (d > dout && !u && T > 0) return fail(-21, "vjf_tangent_rollout: u is required when d > dout");
+    const TgPlan p = tg_plan(n, d, dout, m, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_FC_LOOKAHEAD"));
+    if (!p.fits) return fail(-11, "vjf_tangent_rollout: n=%d, d=%d, dout=%d, m=%d beyond one workgroup's LDS", n, d, dout, m);
+    VjfTgArgs a{};
+    a.u = u; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.x_out = x_out; a.q_out = q_out; a.lsum = lsum; a.lhist = lhist;
+    a.B = B; a.n = n; a.d = d; a.dout = dout; a.m = m; a.qr = qr_every;
+    return tangent_run(a, x0, q0, T, accumulate != 0, p, fc_env_int("VJF_FC_CHUNK"), (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

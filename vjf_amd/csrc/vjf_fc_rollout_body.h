@@ -1,6 +1,7 @@
 // vjf_fc_rollout_body.h -- the body of the roll-out of one tile of trials, included inside vjf_fc_rollout_kernel and
 // vjf_fe_rollout_kernel (no include guard: it is program text of both, so a member of an ensemble computes the roll-out's bits in every
 // form, and the first kernel keeps its instructions).  Expects in scope: `A` (VjfFcArgs), the template parameters NT and CL.
+// KEEP IN STEP with vjf_tangent_kernel.h, whose x step restates this body (features, both MFMA loops, the reduction): a change to one belongs in both.
     constexpr int TB = 16, LD = VJF_LDT, NW = VJF_FC_WAVES, NTH = VJF_FC_THREADS, KQ = VJF_FC_KQ;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int n = A.n, d = A.d, dout = A.dout, du = d - dout, doutp = (dout + 15) / 16 * 16;

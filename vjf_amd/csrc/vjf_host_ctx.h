@@ -77,7 +77,8 @@ const VjfNccl& nccl() {
 //   every call:        VJF_DEBUG_REFUSE_COOP, VJF_DEBUG_ABSENT, VJF_DEBUG_INJECT (filter_seq_mega), VJF_DEBUG_RLSC_ABSENT (launch_rlsb),
 //                      VJF_SEQ_CHUNK (seq_chunk), VJF_DEBUG_TWO_TIMELINE (filter_seq_two); the chaos build: VJF_CHAOS_* (chaos_refresh);
 //                      VJF_FC_CHUNK, VJF_FE_MEMBERS (the entry points vjf_forecast_seq / _ens / _ens_chunks, which hand them to the planners),
-//                      VJF_FC_LOOKAHEAD, VJF_FC_CENTROID_LDS (fc_forms / fe_mom_forms, called by those entry points; vjf_host_forecast.h)
+//                      VJF_FC_LOOKAHEAD, VJF_FC_CENTROID_LDS (fc_forms / fe_mom_forms, called by those entry points; vjf_host_forecast.h);
+//                      VJF_FC_CHUNK, VJF_FC_LOOKAHEAD, VJF_FC_CENTROID_LDS also by vjf_tangent_rollout / _plan (handed to tg_plan, tg_chunk)
 //   once per process:  VJF_RLS_COLUMN_LAUNCHES (launch_rlsb), VJF_NO_MOMENTS_ROLE (mega_shape)
 
 constexpr size_t kMaxLds = 160 * 1024;

@@ -71,6 +71,9 @@ atexit.register(_close_all)
 # what VJF.forecast_ensemble returns: the per-step mean and population variance over the members of the latent state and of the
 # decoder's output, and the members' latent states (S, n_step + 1, B, xdim) or None
 ForecastEnsemble = namedtuple('ForecastEnsemble', ['x_mean', 'x_var', 'y_mean', 'y_var', 'x'])
+# what RBFDS.lyapunov / VJF.lyapunov return: the exponents (B, m) in Gram-Schmidt column order, the final state (B, xdim) and
+# orthonormal frame (B, xdim, m), and the per-interval log R_vv (ceil(n_step / qr_every), B, m) or None
+LyapunovResult = namedtuple('LyapunovResult', ['exponents', 'x', 'q', 'log_stretch'])
 
 
 class LinearDecoder(Module):
@@ -361,6 +364,97 @@ class RBFDS(Module):
                                    N.ptr(x) if T > 0 else None, N.ptr(self._fe_scratch), T, S, B, n, d, dout, dy, stream_ptr()),
                 "vjf_forecast_ens")
         return x_mean, x_var, y_mean, y_var, x
+
+    def _tangent(self, x0, u, q0, n_step, m, qr_every, lsum=None, history=False):
+        """One vjf_tangent_rollout call: (x, q, lsum, lhist).  x0 (B, xdim), u (n_step, B, udim) or None, q0 (B, xdim, m) or None (the
+        first m columns of I), as the library takes them; lsum (B, m): sums to go on from (None: from 0)."""
+        vel = self.velocity
+        B, dout = x0.shape
+        n, d = vel.feature.centroid.shape
+        new = lambda *shape: torch.empty(*shape, device=x0.device, dtype=torch.float32)      # noqa: E731
+        x, q = new(B, dout), new(B, dout, m)
+        accumulate = lsum is not None
+        if qr_every > 0 and lsum is None:
+            lsum = new(B, m)
+        lhist = new(-(-n_step // qr_every), B, m) if history else None
+        N.check(N.lib().vjf_tangent_rollout(N.ptr(x0), N.ptr(u), N.ptr(q0), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                                            N.ptr(vel.w_mean), N.ptr(x), N.ptr(q), N.ptr(lsum), N.ptr(lhist), n_step, B, n, d, dout, m,
+                                            qr_every, int(accumulate), stream_ptr()), "vjf_tangent_rollout")
+        return x, q, lsum, lhist
+
+    def _tangent_u(self, u, T, B):
+        """u as (T, B, udim) on the device, or None for a model without a control input (forecast_sequence's coercion and refusals)."""
+        n, d = self.velocity.feature.centroid.shape
+        du = d - self.velocity.n_output
+        if du == 0:
+            return None
+        if u is None:
+            raise TypeError("u is required when udim > 0")
+        u = dev32(u, ndim2=False)
+        assert u.shape[0] == T, 'u must have length of burn_in + n_step if present'
+        if u.ndim == 2 and B == 1:
+            u = u[:, None, :]
+        assert u.shape == (T, B, du)
+        return u.contiguous()
+
+    def jacobian(self, x: Tensor, u: Tensor = None) -> Tensor:
+        """The Jacobian of the mean map, d/dx of the mean of `forward(x, u, sampling=False)`, as ONE C-ABI call (vjf_tangent_rollout:
+        one step from the identity frame, never normalised):  J = I - w_mean^T G,  G[k, j] = phi_k (x_j - c_kj) / width_k^2.
+        :param x: (B, xdim);  :param u: (B, udim), a parameter of the map, not a direction
+        :return: (B, xdim, xdim), J[b, i, j] = d f_i / d x_j
+        Asynchronous; reads the model's state and writes none."""
+        x = dev32(x)
+        B, dout = x.shape
+        assert dout == self.velocity.n_output, f"x has {dout} columns, expected xdim={self.velocity.n_output}"
+        if u is not None:
+            u = dev32(u)[None]
+        u = self._tangent_u(u, 1, B)
+        return self._tangent(x, u, None, 1, dout, 0)[1]
+
+    def lyapunov(self, x0: Tensor, u: Tensor = None, n_step: int = 1, *, n_exponent: int = None, qr_every: int = 1,
+                 q0: Tensor = None, burn_in: int = 0, dt: float = 1.0, return_history: bool = False) -> LyapunovResult:
+        """The leading Lyapunov exponents of the mean map x[t+1] = x[t] + Phi([x[t], u[t]]) w_mean along the trajectory from `x0`, the
+        whole horizon as ONE C-ABI call (vjf_tangent_rollout): the state and a frame of `n_exponent` tangent vectors per trial stay
+        on chip, the frame is mapped by the Jacobian at every step and re-orthonormalised every `qr_every` steps (and behind the last)
+        by one pass of modified Gram-Schmidt in column order; the logs of the diagonal of R are summed.
+        :param x0: (B, xdim);  :param u: (burn_in + n_step, B, udim) when the model has a control input
+        :param n_exponent: m, 1 <= m <= xdim (default xdim);  :param q0: (B, xdim, m), the frame to start from (default: the first m
+            columns of I); it should be orthonormal, as a returned `q` is
+        :param burn_in: steps that run first through the same entry point; their sums are discarded, the state and frame carry on
+        :param dt: the time one step stands for: exponents = sums / (n_step dt)
+        :return: LyapunovResult(exponents (B, m), x (B, xdim), q (B, xdim, m), log_stretch (ceil(n_step / qr_every), B, m) if
+            `return_history` else None).  The exponents are in Gram-Schmidt column order -- ordered by construction (column v of the
+            frame converges to the v-th most expanding direction), NOT sorted: over a short horizon they need not decrease.  `x` is the
+            final state and `q` the final orthonormal frame: pass them back as `x0` / `q0` (with burn_in = 0) to continue the run; when
+            n_step is a multiple of qr_every the continued run computes the bits of the undivided one.  n_step = 0: x0 itself, q0
+            orthonormalised once, exponents NaN.
+        Asynchronous; reads the model's state and writes none; no scratch."""
+        x0 = dev32(x0)
+        B, dout = x0.shape
+        assert dout == self.velocity.n_output, f"x0 has {dout} columns, expected xdim={self.velocity.n_output}"
+        T, T0, qr = int(n_step), int(burn_in), int(qr_every)
+        assert T >= 0, 'n_step must not be negative'
+        assert T0 >= 0, 'burn_in must not be negative'
+        m = dout if n_exponent is None else int(n_exponent)
+        if not 1 <= m <= dout:
+            raise ValueError(f"n_exponent must be in 1..xdim={dout}, got {n_exponent}")
+        if qr < 1:
+            raise ValueError(f"qr_every must be at least 1, got {qr_every}")
+        dt = float(dt)
+        if not dt > 0.:
+            raise ValueError(f"dt must be positive, got {dt}")
+        if q0 is not None:
+            q0 = dev32(q0, ndim2=False)
+            if q0.ndim == 2 and B == 1:
+                q0 = q0[None]
+            assert q0.shape == (B, dout, m), f"q0 is {tuple(q0.shape)}, expected {(B, dout, m)}"
+            q0 = q0.contiguous()
+        u = self._tangent_u(u, T0 + T, B)
+        if T0 > 0:
+            x0, q0, _, _ = self._tangent(x0, None if u is None else u[:T0], q0, T0, m, qr)
+        x, q, lsum, hist = self._tangent(x0, None if u is None else u[T0:], q0, T, m, qr, history=return_history)
+        exponents = lsum / (T * dt) if T > 0 else torch.full_like(lsum, float('nan'))
+        return LyapunovResult(exponents, x, q, hist)
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1024,3 +1118,15 @@ class VJF(Module):
                  x (S, n_step + 1, B, xdim) if `return_members` else None)"""
         return ForecastEnsemble(*self.transition._forecast_ensemble(self.decoder, x0, u, n_step, n_sample, noise, w_noise, state_noise,
                                                                     x0_noise, return_members))
+
+    def jacobian(self, x: Union[Tensor, Gaussian], u: Tensor = None) -> Tensor:
+        """The Jacobian of the learned mean map at `x` (RBFDS.jacobian); a Gaussian stands for its mean, e.g. the last posterior.
+        :return: (B, xdim, xdim), J[b, i, j] = d f_i / d x_j"""
+        return self.transition.jacobian(x.mean if isinstance(x, Gaussian) else x, u)
+
+    def lyapunov(self, x0: Union[Tensor, Gaussian], u: Tensor = None, n_step: int = 1, *, n_exponent: int = None, qr_every: int = 1,
+                 q0: Tensor = None, burn_in: int = 0, dt: float = 1.0, return_history: bool = False) -> LyapunovResult:
+        """The Lyapunov spectrum of the learned mean map from `x0` in one native call (RBFDS.lyapunov has the arguments and what
+        the columns mean); a Gaussian stands for its mean, e.g. the last posterior `filter` returned."""
+        return self.transition.lyapunov(x0.mean if isinstance(x0, Gaussian) else x0, u, n_step, n_exponent=n_exponent,
+                                        qr_every=qr_every, q0=q0, burn_in=burn_in, dt=dt, return_history=return_history)
