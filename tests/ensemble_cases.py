@@ -21,7 +21,7 @@ LOGVAR0 = math.log(0.04)                 # the Gaussian start's log variance (sd
 MODES = ("quiet", "noisy", "gaussian")   # no state noise / state noise / a Gaussian start (mean fc.inputs' x0), no state noise
 TENSORS = ("x_mean", "x_var", "y_mean", "y_var")
 # The committed factor of the rule.  The issue: start at 4, commit at most twice the worst ratio achieved on the MI355X, never above
-# 16.  Achieved on an MI355X (profiles/ensemble_margins.json, 52 comparisons): the worst ratio is 3.43 (ragged3, S = 8, state noise:
+# 16.  Achieved on an MI355X (profiles/ensemble_margins.json, 60 comparisons): the worst ratio is 3.43 (ragged3, S = 8, state noise:
 # y_var 3.43, x_var 3.03, x_mean 2.16 -- the case whose single roll-out is the forecast suite's worst too); every other case is below
 # 1.8.  F = 4 is within [3.43, 2 * 3.43].
 F = 4.0
@@ -31,7 +31,7 @@ def noises(name):
     """float32 w_noise (S_MAX, T, n, xdim), state_noise (S_MAX, T, B, xdim), x0_noise (S_MAX, B, xdim), all ~ N(0, 1); an ensemble of
     S < S_MAX members takes the first S of each."""
     xdim, udim, n, ydim, B, T = CASES[name]
-    r = np.random.default_rng(3000 + sorted(CASES).index(name))
+    r = np.random.default_rng(3000 + fc.case_index(name))
     f = lambda *s: r.standard_normal(s).astype(np.float32)          # noqa: E731
     return {"w_noise": f(S_MAX, T, n, xdim), "state_noise": f(S_MAX, T, B, xdim), "x0_noise": f(S_MAX, B, xdim)}
 

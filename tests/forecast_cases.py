@@ -19,14 +19,35 @@ CASES = {
     "control": (5, 2, 37, 21, 37, 40),       # control input; n a multiple of neither 4 nor 16
     "wide": (17, 1, 70, 33, 18, 24),         # two output tiles in xdim
     "configB": (10, 0, 200, 50, 33, 24),     # configs[1]'s model dimensions
+    # n beyond what the roll-out kernels' register form of the x step covers (a wavefront's share of K is more than 16 MFMA steps once
+    # n > 256): the planners have to take the streamed form there, and every feature counts
+    "beyond256": (5, 0, 300, 7, 18, 24),
 }
+# seed offsets, fixed per case: a case added later does not move the draws of those before it
+_INDEX = {"configB": 0, "control": 1, "ragged3": 2, "wide": 3, "beyond256": 100}
 HIDDEN = [8]
 EPS32 = float(np.finfo(np.float32).eps)
 # The committed factor of the rule.  The issue: start at 4, commit at most twice the worst ratio achieved on the MI355X, never above
 # 16.  Achieved on an MI355X (profiles/forecast_margins.json): the worst ratio is 2.95 (ragged3 without state noise: x 2.91, y 2.95 --
 # 40 steps of a map that stretches a rounding difference, the fp32 oracle's own E being one draw of the same amplification); every
 # other comparison is between 0.12 and 1.08.  F = 4 is within [2.95, 2 * 2.95].
+# `beyond256` without state noise reaches 6.56 in x (y 6.43; with state noise 1.86 and 2.73, inside F): 300 features summed in one fp32
+# accumulator per weight sample and per K share, then 24 steps of the same amplification with no noise to cover it.  Every feature is
+# counted: test_gpu_tangent.py::test_final_state_against_forecast_sequence finds the tangent kernel's final x at this shape equal to
+# this kernel's bit for bit, and that x lies 0.23 of its bound from fp64 (profiles/tangent_margins.json).  By the same policy the
+# comparison without state noise of that case alone is held to 8 <= 2 * 6.56; everything else stays at 4.
 F = 4.0
+F_CASE = {("beyond256", False): 8.0}
+
+
+def factor(name, state_noise):
+    """The committed factor of the rule for a case, with or without state noise."""
+    return F_CASE.get((name, bool(state_noise)), F)
+
+
+def case_index(name):
+    """The case's seed offset (state 1000 +, inputs 2000 +, the ensemble's draws 3000 +)."""
+    return _INDEX[name]
 
 
 def synthetic_state(seed, xdim, udim, n, ydim):
@@ -47,8 +68,7 @@ def make_model(vjf, name, **kw):
     torch.manual_seed(5)
     m = vjf.VJF.make_model(ydim, xdim, udim, n, HIDDEN, likelihood="gaussian", **kw)
     views = model_arrays(m)
-    seed = 1000 + sorted(CASES).index(name)
-    for k, a in synthetic_state(seed, xdim, udim, n, ydim).items():
+    for k, a in synthetic_state(1000 + case_index(name), xdim, udim, n, ydim).items():
         views[k].copy_(torch.as_tensor(a).reshape(views[k].shape).to(views[k].device))
     return m
 
@@ -56,7 +76,7 @@ def make_model(vjf, name, **kw):
 def inputs(name):
     """float32 arrays x0 (B,xdim), u (T,B,udim) or None, w_noise (T,n,xdim), state_noise (T,B,xdim), all ~ N(0,1)."""
     xdim, udim, n, ydim, B, T = CASES[name]
-    r = np.random.default_rng(2000 + sorted(CASES).index(name))
+    r = np.random.default_rng(2000 + case_index(name))
     f = lambda *s: r.standard_normal(s).astype(np.float32)          # noqa: E731
     return {"x0": f(B, xdim), "u": f(T, B, udim) if udim else None, "w_noise": f(T, n, xdim), "state_noise": f(T, B, xdim)}
 

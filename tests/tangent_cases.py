@@ -16,9 +16,7 @@ from tests import forecast_cases as fc
 from tests import tangent_ref as tr
 from tests.helpers import load_oracle_state, model_arrays
 
-# forecast_cases' four shapes, and one whose n is beyond what the kernel's register form of the x step covers (a wavefront's share of
-# K is more than 16 MFMA steps once n > 256): the planner has to take the other form there
-CASES = dict(fc.CASES, beyond256=(5, 0, 300, 7, 18, 24))   # (xdim, udim, n_rbf, ydim, B, T)
+CASES = fc.CASES                         # (xdim, udim, n_rbf, ydim, B, T); `beyond256`: the x step's streamed form is the only right one
 EPS32 = fc.EPS32
 W_SCALE = 10.0
 # (m, qr_every) of the parity test; m = None: xdim.  (None, 3) ends with a ragged interval (T = 40: 13 x 3 + 1; T = 24: a whole one)
@@ -30,9 +28,7 @@ PARITY = [(None, 1), (2, 4), (None, 3)]
 F = 2.3
 
 
-def case_index(name):
-    """The case's seed offset: forecast_cases' own for its four cases, 100 for the one defined here."""
-    return sorted(fc.CASES).index(name) if name in fc.CASES else 100
+case_index = fc.case_index
 
 
 def state(name, dtype=np.float64):
@@ -59,14 +55,9 @@ def make_model(vjf, name, **kw):
 
 
 def inputs(name):
-    """float32 arrays x0 (B, xdim), u (T, B, udim) or None, ~ N(0, 1): forecast_cases' own draws for its cases."""
-    if name in fc.CASES:
-        a = fc.inputs(name)
-        return {"x0": a["x0"], "u": a["u"]}
-    xdim, udim, n, ydim, B, T = CASES[name]
-    r = np.random.default_rng(2000 + case_index(name))
-    f = lambda *s: r.standard_normal(s).astype(np.float32)          # noqa: E731
-    return {"x0": f(B, xdim), "u": f(T, B, udim) if udim else None}
+    """float32 arrays x0 (B, xdim), u (T, B, udim) or None, ~ N(0, 1): forecast_cases' own draws."""
+    a = fc.inputs(name)
+    return {"x0": a["x0"], "u": a["u"]}
 
 
 def references(s64, x0, u, T, m, qr_every, q0=None, lsum0=None):

@@ -76,8 +76,8 @@ def test_parity_against_the_fp64_oracle(vjf, name, state_noise):
                                state_noise=t["state_noise"] if state_noise else None)
     assert x.shape == x64.shape and y.shape == y64.shape
     same_bits(x[0], t["x0"], "x[0]")
-    by_rule(f"{name} x", x, x64, x32)
-    by_rule(f"{name} y", y, y64, y32)
+    by_rule(f"{name} x", x, x64, x32, fc.factor(name, state_noise))
+    by_rule(f"{name} y", y, y64, y32, fc.factor(name, state_noise))
 
 
 # ------------------------------------------------------------------ 2

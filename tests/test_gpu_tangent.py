@@ -241,13 +241,12 @@ def test_the_returned_frame_is_orthonormal(vjf, name):
 
 
 # ------------------------------------------------------------------ 6
-@pytest.mark.parametrize("name", [k for k in tc.CASES if tc.CASES[k][2] <= 256])
+@pytest.mark.parametrize("name", list(tc.CASES))
 def test_final_state_against_forecast_sequence(vjf, name):
     """The same map on another kernel: forecast_sequence with zero weight noise and no state noise ends where lyapunov ends.  The two
     final states against each other under the rule's bound of x (E from the fp32 reference), and lyapunov's against the fp64
-    trajectory with E the roll-out kernel's own distance from it.  The cases of up to 256 features: beyond that the roll-out kernel's
-    own planner (fc_forms) still takes its register form, which covers 64 features per wavefront -- its fix is its own change, and
-    `beyond256` is held against the fp64 reference by the parity tests above."""
+    trajectory with E the roll-out kernel's own distance from it.  Every case: the two kernels share one x step and one planner of
+    its forms, `beyond256` being the shape at which both have to take the streamed one."""
     xdim, udim, n, ydim, B, T = tc.CASES[name]
     model, t, _ = case(vjf, name)
     xs = model.transition.forecast_sequence(t["x0"], t["u"], T, w_noise=torch.zeros(T, n, xdim, device="cuda"))

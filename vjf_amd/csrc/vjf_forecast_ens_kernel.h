@@ -2,7 +2,7 @@
 // predictive distribution each) and their per-step mean and variance, as three kernels per chunk of members x steps:
 //
 //   vjf_fe_weights_kernel   W[s][t] = w_mean + w_chol @ w_noise[s][t]  (vjf/module.py:70-73) for every member and step of the chunk:
-//                           vjf_fc_weights_kernel's sample body, the member on the flattened sample index.
+//                           vjf_fc_weights_kernel's sample (fc_sample), the member on the flattened sample index.
 //   vjf_fe_rollout_kernel   one workgroup per (tile of 16 trials, member): vjf_fc_rollout_kernel's body on the member's W, noise and start.
 //   vjf_fe_moments_kernel   one workgroup per (tile of 16 trials, step, group of 8 output tiles): walks the chunk's members in member
 //                           order, decodes y = x C^T + b on chip (vjf/model.py:321-324) and folds x and y into running (mean, M2).
@@ -12,7 +12,7 @@
 // Included by vjf_host_forecast.h.  The kernels sit in an anonymous namespace: their symbols carry it.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_forecast_kernel.h"     // VjfFcArgs, fc_k_range, VJF_FC_*
+#include "vjf_forecast_kernel.h"     // VjfFcArgs, fc_rollout, fc_sample, VJF_FC_*
 
 namespace {
 struct VjfFeWeightArgs {
@@ -24,22 +24,16 @@ struct VjfFeWeightArgs {
 };
 
 // Workgroup (m, g): rows 16 m .. 16 m + 15 of the samples q = sl Tc + t with q = 4 g + wave (mod 4 gridDim.y).  One wavefront, one
-// accumulator, k ascending per sample (vjf_fc_sample_body.h): the bits of W[s][t] depend on that sample's inputs alone.
+// accumulator, k ascending per sample (fc_sample): the bits of W[s][t] depend on that sample's inputs alone.
 __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fe_weights_kernel(VjfFeWeightArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* s_a = smem;                                   // n x LD
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m0 = blockIdx.x * 16, n = A.n, dout = A.dout;
-    for (int e = tid; e < 16 * n; e += VJF_FC_THREADS) {
-        const int i = e / n, k = e - i * n;              // (consecutive lanes: consecutive k of one row)
-        s_a[k * VJF_LDT + i] = (m0 + i) < n ? A.w_chol[(size_t)(m0 + i) * n + k] : 0.f;
-    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m0 = blockIdx.x * 16, n = A.n, dout = A.dout, nq = A.Sc * A.Tc;
+    fc_stage_chol(smem, A.w_chol, m0, n);
     __syncthreads();
-    const int col = lane & 15, r4 = 4 * (lane >> 4), nq = A.Sc * A.Tc;
     for (int q = blockIdx.y * VJF_FC_WAVES + wave; q < nq; q += gridDim.y * VJF_FC_WAVES) {
         const int sl = q / A.Tc, t = q - sl * A.Tc;
-        const float* nz = A.noise + (size_t)sl * A.noise_ms + (size_t)t * n * dout;
-        float* Wt = A.W + (size_t)q * n * dout;
-#include "vjf_fc_sample_body.h"
+        for (int j0 = 0; j0 < dout; j0 += 16)
+            fc_sample(A.noise + (size_t)sl * A.noise_ms + (size_t)t * n * dout, A.W + (size_t)q * n * dout, A.w_mean, smem, m0, n, dout, j0, lane);
     }
 }
 
@@ -48,20 +42,18 @@ struct VjfFeArgs {
     size_t x_in_ms, e_ms, W_ms, x0_out_ms, x_out_ms;     // distance of two members in x_in, e, W, x0_out, x_out (floats)
 };
 
-// blockIdx.y: the member.  The step loop is vjf_fc_rollout_kernel's own text (vjf_fc_rollout_body.h), so member s computes
+// blockIdx.y: the member.  The step loop is vjf_fc_rollout_kernel's own (fc_rollout), so member s computes
 // vjf_forecast_seq's bits on member s's inputs in every form of the kernel (look-ahead, W from L2, centroids in LDS or global memory).
 template <int NT, bool CL>
 __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fe_rollout_kernel(VjfFeArgs E) {
     VjfFcArgs A = E.a;
-    {
-        const size_t s = blockIdx.y;
-        A.x_in += s * E.x_in_ms;
-        if (A.e) A.e += s * E.e_ms;
-        A.W += s * E.W_ms;
-        if (A.x0_out) A.x0_out += s * E.x0_out_ms;
-        A.x_out += s * E.x_out_ms;
-    }
-#include "vjf_fc_rollout_body.h"
+    const size_t s = blockIdx.y;
+    A.x_in += s * E.x_in_ms;
+    if (A.e) A.e += s * E.e_ms;
+    A.W += s * E.W_ms;
+    if (A.x0_out) A.x0_out += s * E.x0_out_ms;
+    A.x_out += s * E.x_out_ms;
+    fc_rollout<NT, CL>(A);
 }
 
 #define VJF_FE_THREADS 256

@@ -92,7 +92,7 @@ size_t fe_x_bytes(int T, int S, int B, int dout) {
 struct FcForms { bool fits, cl, la; size_t lds, lds_w; };   // fits LDS at all (else the entry point refuses); centroids in LDS; look-ahead; dynamic LDS: roll-out, weights
 FcForms fc_forms(int n, int d, int dout) {
     const bool cl = vjf_fc_lds_floats(n, d, dout, true) * 4 <= kMaxLds - 1024 && fc_env_on("VJF_FC_CENTROID_LDS");
-    const bool la = cl && n <= 64 * VJF_FC_KQ && dout <= 32 && fc_env_on("VJF_FC_LOOKAHEAD");
+    const bool la = cl && vjf_fc_reg_form(n, dout) && fc_env_on("VJF_FC_LOOKAHEAD");
     return FcForms{vjf_fc_lds_floats(n, d, dout, false) * 4 <= kMaxLds - 1024, cl, la, vjf_fc_lds_floats(n, d, dout, cl) * 4, (size_t)n * VJF_LDT * 4};
 }
 // the moments kernel: the same two switches also take the decoder out of LDS and the batched staging out of the kernel
@@ -102,11 +102,12 @@ FeMomForms fe_mom_forms(int dout, int dy) {
     const bool dl = dy > 0 && vjf_fe_lds_floats(dout, mb, true) * 4 <= kMaxLds / 2 && fc_env_on("VJF_FC_CENTROID_LDS");
     return FeMomForms{mb, dl, vjf_fe_lds_floats(dout, mb, dl) * 4};
 }
-// f(NT, CL) with the roll-out's template arguments as std::integral_constant / std::bool_constant values
-template <class F> void with_fc_form(const FcForms& fm, int dout, F&& f) {
-    if (fm.la && dout <= 16) f(std::integral_constant<int, 1>{}, std::true_type{});
-    else if (fm.la) f(std::integral_constant<int, 2>{}, std::true_type{});
-    else if (fm.cl) f(std::integral_constant<int, 0>{}, std::true_type{});
+// f(NT, CL) with the x step's template arguments as std::integral_constant / std::bool_constant values: the one dispatch on the two
+// switches (la implies cl), for the roll-out kernels and the tangent kernel
+template <class F> void with_fc_form(bool la, bool cl, int dout, F&& f) {
+    if (la && dout <= 16) f(std::integral_constant<int, 1>{}, std::true_type{});
+    else if (la) f(std::integral_constant<int, 2>{}, std::true_type{});
+    else if (cl) f(std::integral_constant<int, 0>{}, std::true_type{});
     else f(std::integral_constant<int, 0>{}, std::false_type{});
 }
 template <class F> void with_fe_mom_form(const FeMomForms& fm, F&& f) { if (fm.dl) f(std::true_type{}); else f(std::false_type{}); }
@@ -184,7 +185,7 @@ int forecast_run(const VjfFcArgs& base, const float* w_mean, const float* w_chol
             e.a = fc_chunk_args(base, W, s_noise ? s_noise + (size_t)ms0 * T * xstep : nullptr, t0, Tc, x_in, rows + xstep);
             e.x_in_ms = t0 == 0 ? x0_ms : xs_ms; e.e_ms = (size_t)T * xstep; e.W_ms = (size_t)Tc * wstep;
             e.x0_out_ms = t0 == 0 ? xs_ms : 0; e.x_out_ms = xs_ms;
-            with_fc_form(fm, dout, [&](auto nt, auto cl) {
+            with_fc_form(fm.la, fm.cl, dout, [&](auto nt, auto cl) {
                 constexpr int NT = decltype(nt)::value;
                 constexpr bool CL = decltype(cl)::value;
                 if (ens) {

@@ -8,13 +8,12 @@ namespace {
 
 // ---- planner.  The frame, the sums and one pass's partial products are in LDS beside the roll-out's buffers: `vg` tangent vectors per
 //      pass, as many as fit (all m wherever the model dimensions are moderate; the bits do not depend on it).  cl: centroids and w_mean
-//      in LDS (`cen_lds`: VJF_FC_CENTROID_LDS); la: w_mean's x-step operands in registers (`lookahead`: VJF_FC_LOOKAHEAD); no: output
-//      tiles of the second product.  fits == false: the entry point refuses (dout beyond VJF_TG_MAXDOUT, or not one pass fits).
-struct TgPlan { bool fits, cl, la; int vg, no; size_t lds; };
+//      in LDS (`cen_lds`: VJF_FC_CENTROID_LDS); la: w_mean's x-step operands in registers (`lookahead`: VJF_FC_LOOKAHEAD).
+//      fits == false: the entry point refuses (dout beyond VJF_TG_MAXDOUT, or not one pass fits).
+struct TgPlan { bool fits, cl, la; int vg; size_t lds; };
 TgPlan tg_plan(int n, int d, int dout, int m, bool cen_lds, bool lookahead) {
     const size_t budget = kMaxLds - 1024;
     TgPlan p{};
-    p.no = dout <= 16 ? 1 : (dout <= 32 ? 2 : 4);
     if (dout > VJF_TG_MAXDOUT) return p;
     p.cl = cen_lds && vjf_tangent_lds_floats(n, d, dout, m, m, true) * 4 <= budget;
     int vg = m;
@@ -22,8 +21,7 @@ TgPlan tg_plan(int n, int d, int dout, int m, bool cen_lds, bool lookahead) {
     if (vg < 1) return p;
     p.fits = true;
     p.vg = vg;
-    // (the register form holds VJF_FC_KQ MFMA steps of a wavefront's share of K, 4 features each: n <= 4 VJF_FC_WAVES VJF_FC_KQ = 256)
-    p.la = p.cl && lookahead && n <= 4 * VJF_FC_WAVES * VJF_FC_KQ && dout <= 32;
+    p.la = p.cl && lookahead && vjf_fc_reg_form(n, dout);
     p.lds = vjf_tangent_lds_floats(n, d, dout, m, vg, p.cl) * 4;
     return p;
 }
@@ -35,17 +33,15 @@ int tg_chunk(int qr, int chunk) {
     return c;
 }
 
-// f(NT, CL, NO) with the kernel's template arguments as std::integral_constant / std::bool_constant values
-template <class F> void with_tg_form(const TgPlan& p, F&& f) {
-    using std::integral_constant;
-    if (p.la && p.no == 1) f(integral_constant<int, 1>{}, std::true_type{}, integral_constant<int, 1>{});
-    else if (p.la) f(integral_constant<int, 2>{}, std::true_type{}, integral_constant<int, 2>{});
-    else if (p.cl && p.no == 1) f(integral_constant<int, 0>{}, std::true_type{}, integral_constant<int, 1>{});
-    else if (p.cl && p.no == 2) f(integral_constant<int, 0>{}, std::true_type{}, integral_constant<int, 2>{});
-    else if (p.cl) f(integral_constant<int, 0>{}, std::true_type{}, integral_constant<int, 4>{});
-    else if (p.no == 1) f(integral_constant<int, 0>{}, std::false_type{}, integral_constant<int, 1>{});
-    else if (p.no == 2) f(integral_constant<int, 0>{}, std::false_type{}, integral_constant<int, 2>{});
-    else f(integral_constant<int, 0>{}, std::false_type{}, integral_constant<int, 4>{});
+// f(NT, CL, NO) with the kernel's template arguments as std::integral_constant / std::bool_constant values: the x step's dispatch
+// (with_fc_form) and NO, the tiles of 16 that cover dout (1, 2 or 4) -- in the register form that is NT itself, so NT is passed on
+template <class F> void with_tg_form(const TgPlan& p, int dout, F&& f) {
+    with_fc_form(p.la, p.cl, dout, [&](auto nt, auto cl) {
+        if constexpr (decltype(nt)::value > 0) f(nt, cl, nt);
+        else if (dout <= 16) f(nt, cl, std::integral_constant<int, 1>{});
+        else if (dout <= 32) f(nt, cl, std::integral_constant<int, 2>{});
+        else f(nt, cl, std::integral_constant<int, 4>{});
+    });
 }
 
 // ---- the call behind its argument checks.  `a`: what the chunks share (u, c, logw, w, the outputs and the sizes, filled by the entry
@@ -66,7 +62,7 @@ int tangent_run(VjfTgArgs a, const float* x0, const float* q0, int T, bool accum
         a.Tc = Tc; a.last = t0 + Tc == T;
         a.tq = a.qr > 0 ? t0 % a.qr : 0;
         a.lhist = lhist && a.qr > 0 ? lhist + (size_t)(t0 / a.qr) * B * a.m : nullptr;
-        with_tg_form(p, [&](auto nt, auto cl, auto no) {
+        with_tg_form(p, a.dout, [&](auto nt, auto cl, auto no) {
             auto kernel = vjf_tangent_rollout_kernel<decltype(nt)::value, decltype(cl)::value, decltype(no)::value>;
             allow_lds(kernel, p.lds);
             hipLaunchKernelGGL(kernel, dim3(tiles), dim3(VJF_FC_THREADS), p.lds, s, a);

@@ -5,7 +5,7 @@
 //                                the tangent frame Q (dout x m per trial) in LDS:  features of [x_t, u_t] -> x_{t+1} = x_t + Phi w_mean
 //                                -> V = J(x_t, u_t) Q -> every `qr` steps one pass of modified Gram-Schmidt on V, log R_ii summed.
 //
-// The x step is vjf_fc_rollout_kernel's (same tiling, same MFMA steps, W[t] = w_mean for every t).  J q = q - w_mean^T s with
+// The x step is vjf_fc_rollout_kernel's (vjf_rollout_step.h: same tiling, same MFMA steps, W[t] = w_mean for every t).  J q = q - w_mean^T s with
 // s_k = (phi_k / width_k^2)(x^T q - (C_x q)_k): two products with matrices every trial and every tangent vector share, so tangent
 // vector v of the tile's 16 trials is one tile of 16 MFMA columns, [v][component][VJF_LDT] in LDS.  Per tile of 16 features a wavefront
 // computes C_x Q_v (K = dout), scales the 16 x 16 accumulator in registers and feeds it back as the B operand of w_mean^T s: the
@@ -13,12 +13,9 @@
 // rows 4 kk + r of w_mean as its A operand -- a permutation of K, no trip through LDS.  K (the feature tiles) is split over the four
 // wavefronts, tile ft to wavefront ft mod 4, and the four partial products are added in a fixed order.
 // Workgroups are independent: no cooperative launch, no hand-off.  Included by vjf_host_tangent.h.
-// KEEP IN STEP with vjf_fc_rollout_body.h: the x step here (features, the NT > 0 and NT == 0 MFMA loops, the reduction, the look-ahead
-// of u) restates that body without its per-step stores, its noise and its W[t] fetches; a change to one belongs in both.  The register
-// form (NT > 0) covers VJF_FC_KQ steps of 4 features per wavefront: the planner (tg_plan) must keep it to n <= 4 VJF_FC_WAVES VJF_FC_KQ.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_forecast_kernel.h"     // VJF_FC_THREADS / _WAVES / _KQ, fc_k_range, vjf_f32x4, VJF_LDT
+#include "vjf_forecast_kernel.h"     // vjf_rollout_step.h: the x step, FcTile, VJF_FC_THREADS / _WAVES / _KQ, vjf_f32x4, VJF_LDT
 
 #define VJF_TG_MV 4                  // tangent vectors whose accumulators a wavefront holds while it walks its feature tiles
 #define VJF_TG_MAXDOUT 64            // dout <= 64: C_x Q is at most 16 MFMA steps deep, w_mean^T s at most 4 output tiles
@@ -42,10 +39,11 @@ struct VjfTgArgs {
     int vg;                  // tangent vectors per pass (the partial products of a pass are in LDS together)
 };
 
+// the x step's buffers plus 1 / width^2, the frame, x^T q and the sums, one pass's partial products and (cen_lds) w_mean
 static inline size_t vjf_tangent_lds_floats(int n, int d, int dout, int m, int vg, bool cen_lds) {
     const size_t doutp = ((size_t)dout + 15) / 16 * 16, LD = VJF_LDT;
-    return (size_t)n * LD + (size_t)d * LD + (size_t)VJF_FC_WAVES * doutp * LD + 2 * (size_t)n + (size_t)m * dout * LD + 2 * (size_t)m * LD +
-           (size_t)VJF_FC_WAVES * vg * doutp * LD + (cen_lds ? (size_t)n * d + (size_t)n * dout : 0);
+    return vjf_fc_lds_floats(n, d, dout, cen_lds) + (size_t)n + (size_t)m * dout * LD + 2 * (size_t)m * LD +
+           (size_t)VJF_FC_WAVES * vg * doutp * LD + (cen_lds ? (size_t)n * dout : 0);
 }
 
 // NT, CL: vjf_fc_rollout_kernel's forms of the x step (NT > 0: this lane's elements of w_mean stay in registers for the whole chunk;
@@ -54,37 +52,24 @@ static inline size_t vjf_tangent_lds_floats(int n, int d, int dout, int m, int v
 // NO: output tiles of w_mean^T s, dout <= 16 NO.
 template <int NT, bool CL, int NO>
 __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_tangent_rollout_kernel(VjfTgArgs A) {
-    constexpr int TB = 16, LD = VJF_LDT, NW = VJF_FC_WAVES, NTH = VJF_FC_THREADS, KQ = VJF_FC_KQ, MV = VJF_TG_MV;
+    constexpr int TB = 16, LD = VJF_LDT, NW = VJF_FC_WAVES, NTH = VJF_FC_THREADS, MV = VJF_TG_MV;
+    static_assert(NT == 0 || NT == NO, "the register form of the x step covers dout <= 16 NT: the same tiles as NO");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int n = A.n, d = A.d, dout = A.dout, du = d - dout, m = A.m, vg = A.vg, doutp = (dout + 15) / 16 * 16;
-    float* s_phi = smem;                          // n x LD       features of step t
-    float* s_x = s_phi + n * LD;                  // d x LD       [x_t, u_t]
-    float* s_part = s_x + d * LD;                 // NW x doutp x LD   the wavefronts' partial products of the x step
-    float* s_w2 = s_part + NW * doutp * LD;       // n            width^2
-    float* s_iw2 = s_w2 + n;                      // n            1 / width^2
+    FcTile S = fc_tile(smem, A.n, A.d, A.dout, A.B);     // s_phi, s_x, s_part, s_w2: the x step's
+    const int n = S.n, d = S.d, dout = S.dout, du = S.du, m = A.m, vg = A.vg, doutp = S.doutp;
+    float *s_phi = S.s_phi, *s_x = S.s_x;
+    float* s_iw2 = S.rest;                        // n            1 / width^2
     float* s_q = s_iw2 + n;                       // m x dout x LD     the frame: [v][j][trial]
     float* s_xq = s_q + m * dout * LD;            // m x LD       x_t^T q_v
     float* s_ls = s_xq + m * LD;                  // m x LD       running sums of log R_vv
     float* s_vp = s_ls + m * LD;                  // NW x vg x doutp x LD   the wavefronts' partial products of w_mean^T s, one pass
-    float* s_c = s_vp + NW * vg * doutp * LD;     // n x d        centroids (CL)
-    float* s_wm = s_c + n * d;                    // n x dout     w_mean (CL)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b0 = blockIdx.x * TB, nb = min(TB, A.B - b0);
+    const float* s_c = S.s_c = s_vp + NW * vg * doutp * LD;   // n x d   centroids (CL): behind this kernel's buffers
+    float* s_wm = S.s_c + n * d;                  // n x dout     w_mean (CL)
+    const int tid = S.tid, lane = S.lane, wave = S.wave, b0 = S.b0, nb = S.nb, mi = S.mi, kk = S.kk, r4 = S.r4, nft = (n + 15) / 16;
     const size_t row0 = (size_t)b0 * dout, su = (size_t)A.B * du, qrow0 = (size_t)b0 * dout * m, bm = (size_t)A.B * m;
 
-    for (int k = tid; k < n; k += NTH) { const float w = expf(A.logw[k]); s_w2[k] = w * w; s_iw2[k] = 1.f / (w * w); }
-    if (CL) {
-        for (int i = tid; i < n * d; i += NTH) s_c[i] = A.c[i];
-        for (int i = tid; i < n * dout; i += NTH) s_wm[i] = A.w[i];
-    }
-    for (int i = tid; i < TB * dout; i += NTH) {
-        const int b = i / dout, j = i - b * dout;
-        s_x[j * LD + b] = b < nb ? A.x_in[row0 + i] : 0.f;
-    }
-    if (A.Tc > 0)
-        for (int i = tid; i < TB * du; i += NTH) {
-            const int b = i / du, j = i - b * du;
-            s_x[(dout + j) * LD + b] = b < nb ? A.u[(size_t)b0 * du + i] : 0.f;
-        }
+    fc_stage<CL, true>(S, A.logw, A.c, s_iw2, A.x_in, nullptr, A.Tc > 0 ? A.u : nullptr);
+    if (CL) for (int i = tid; i < n * dout; i += NTH) s_wm[i] = A.w[i];
     for (int i = tid; i < TB * dout * m; i += NTH) {
         const int b = i / (dout * m), r = i - b * dout * m, j = r / m, v = r - j * m;
         float q = 0.f;
@@ -95,21 +80,8 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_tangent_rollout_kernel(Vjf
         const int b = i / m, v = i - b * m;
         s_ls[v * LD + b] = (b < nb && A.lsum_in) ? A.lsum_in[(size_t)b0 * m + i] : 0.f;
     }
-    int kb, ke;
-    fc_k_range(n, wave, kb, ke);
-    const int mi = lane & 15, kk = lane >> 4, r4 = 4 * (lane >> 4), nft = (n + 15) / 16;
-    constexpr int NTR = NT > 0 ? NT : 1;
-    float aw[NTR][KQ];                                    // (NT > 0) this lane's A operands of the x step: w_mean, the same at every step
-    if (NT > 0) {
-#pragma unroll
-        for (int t = 0; t < NTR; ++t)
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const int k = kb + 4 * q + kk, j = t * 16 + mi;
-                const bool ok = k < ke && j < dout;
-                aw[t][q] = A.w[ok ? (size_t)k * dout + j : 0];
-            }
-    }
+    float aw[NT > 0 ? NT : 1][VJF_FC_KQ];                // (NT > 0) this lane's A operands of the x step: w_mean, the same at every step
+    if constexpr (NT > 0) fc_fetch_w(S, A.w, aw);
 
     // One pass of modified Gram-Schmidt in column order on every trial's frame, in place: a wavefront takes four trials, sixteen lanes
     // each; lane g of a trial owns components g, g + 16, .. of every column and reads and writes nothing else, so the pass needs no
@@ -170,20 +142,9 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_tangent_rollout_kernel(Vjf
 
     for (int t = 0; t < A.Tc; ++t) {
         // the next step's control input: in flight while the features are computed
-        float u0 = 0.f;
-        if (du > 0 && t + 1 < A.Tc && tid < nb * du) u0 = A.u[(size_t)(t + 1) * su + (size_t)b0 * du + tid];
-
-        // features: exp(-1/2 |xu - c|^2 / width^2), the squared distance as a sum of squared differences (the roll-out's)
-        for (int i = tid; i < TB * n; i += NTH) {
-            const int k = i / TB, b = i - k * TB;
-            float ph = 0.f;
-            if (b < nb) {
-                float d2 = 0.f;
-                for (int j = 0; j < d; ++j) { const float df = s_x[j * LD + b] - (CL ? s_c[k * d + j] : A.c[(size_t)k * d + j]); d2 = fmaf(df, df, d2); }
-                ph = expf(-0.5f * d2 / s_w2[k]);
-            }
-            s_phi[k * LD + b] = ph;
-        }
+        const float* un = du > 0 && t + 1 < A.Tc ? A.u + (size_t)(t + 1) * su + (size_t)b0 * du : nullptr;
+        const float u0 = fc_u_ahead(S, un);
+        fc_features<CL>(S, A.c);
         // x_t^T q_v
         for (int i = tid; i < TB * m; i += NTH) {
             const int v = i / TB, b = i - v * TB;
@@ -193,39 +154,9 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_tangent_rollout_kernel(Vjf
         }
         __syncthreads();
 
-        // Phi w_mean, K split over the four wavefronts as in the roll-out: partial(row j, col trial) of features kb .. ke - 1
-        if (NT > 0) {
-#pragma unroll
-            for (int tl = 0; tl < NTR; ++tl) {
-                vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                const bool rv = tl * 16 + mi < dout;
-#pragma unroll
-                for (int q = 0; q < KQ; ++q) {
-                    const int k0 = kb + 4 * q;
-                    if (k0 < ke) {                                       // (uniform over the wavefront)
-                        const bool kv = k0 + kk < ke;
-                        const float xv = s_phi[(kv ? k0 + kk : kb) * LD + mi];
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32((rv && kv) ? aw[tl][q] : 0.f, kv ? xv : 0.f, acc, 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s_part[(wave * doutp + tl * 16 + r4 + r) * LD + mi] = acc[r];
-            }
-        } else {
-            // (the same steps in the same order on operands read when they are used, every address inside w_mean)
-            for (int j0 = 0; j0 < dout; j0 += 16) {
-                vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                const bool rv = j0 + mi < dout;
-                for (int k0 = kb; k0 < ke; k0 += 4) {
-                    const bool kv = k0 + kk < ke, ok = rv && kv;
-                    const float av = CL ? s_wm[ok ? (k0 + kk) * dout + j0 + mi : 0] : A.w[ok ? (size_t)(k0 + kk) * dout + j0 + mi : 0];
-                    const float xv = s_phi[(kv ? k0 + kk : kb) * LD + mi];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ok ? av : 0.f, kv ? xv : 0.f, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s_part[(wave * doutp + j0 + r4 + r) * LD + mi] = acc[r];
-            }
-        }
+        // Phi w_mean, K split over the four wavefronts as in the roll-out (streamed: every address inside w_mean)
+        if constexpr (NT > 0) fc_product_reg(S, aw);
+        else fc_product_masked(S, CL ? s_wm : A.w);
 
         // V = Q - w_mean^T s, `vg` tangent vectors per pass
         for (int v0 = 0; v0 < m; v0 += vg) {
@@ -316,18 +247,8 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_tangent_rollout_kernel(Vjf
         }
 
         // x_{t+1} = x_t + (p0 + p1 + p2 + p3)
-        for (int i = tid; i < nb * dout; i += NTH) {
-            const int b = i / dout, j = i - b * dout;
-            float v = s_part[j * LD + b];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) v += s_part[(w * doutp + j) * LD + b];
-            s_x[j * LD + b] = s_x[j * LD + b] + v;
-        }
-        if (du > 0 && t + 1 < A.Tc)
-            for (int i = tid; i < nb * du; i += NTH) {
-                const int b = i / du, j = i - b * du;
-                s_x[(dout + j) * LD + b] = i == tid ? u0 : A.u[(size_t)(t + 1) * su + (size_t)b0 * du + i];
-            }
+        fc_advance(S, [](int, float v) { return v; });
+        fc_u_advance(S, un, u0);
         __syncthreads();
 
         if (A.qr > 0 && ((A.tq + t + 1) % A.qr == 0 || (A.last && t + 1 == A.Tc))) {
