@@ -87,7 +87,7 @@ ALLOW = {
     ("vjf_chol_kernel.h", "for (int q = 0; q < 8; ++q) gv[q] = (cb + 4 * q < c1) ? *reinterpret_cast<const float4*>(grow + cb + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);"): "other: !A.post",
     ("vjf_chol_kernel.h", "for (int j = 0; j < dz; ++j) f = fmaf(s_g[i * DZP + j], FDX[(size_t)i * dz + j], f);"): "other: !A.post",
     ("vjf_chol_kernel.h", "double t = (double)it_red[P.red_SC + RS_SDX2];"): "other: !A.post",
-    ("vjf_chol_kernel.h", "const float acc = fminf(SC[VJF_SC_N_TR], 500.f), tot = acc + Bf;   // running_var, size_cap=500 (model.py:375)"): "other: !A.post",
+    ("vjf_chol_kernel.h", "S[P.off[VJF_SLOT_TR_LOGVAR]] = vjf_running_logvar(sig, SC[VJF_SC_N_TR], VJF_TR_VAR_CAP, Bf, vjf_resid_mse(t, Bf, dz), tot);"): "other: !A.post",
 }
 
 

@@ -150,7 +150,7 @@ int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t
     allow_lds(vjf_serial_kernel, c->lds_k2);
     allow_lds(vjf_rls_post_kernel, c->lds_post);
     allow_lds(vjf_prepg_kernel, vjf_prepg_lds_bytes(P));
-    if (c->mfma_trial) allow_lds(vjf_trial_mfma_kernel, c->lds_k1m);
+    if (c->mfma_trial) allow_lds(vjf_trial_mfma_kernel<>, c->lds_k1m);
     allow_lds(chol_kernels(P.dz).chol, c->lds_chol);        // (the instantiations this context launches)
     if (P.dz <= 16) allow_lds(chol_kernels(P.dz).pair, c->lds_chol);
     mega_residency(c);

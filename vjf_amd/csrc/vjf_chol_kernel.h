@@ -16,6 +16,7 @@
 #include "vjf_gram_kernel.h"   // vjf_f32x16
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
+#include "vjf_step_math.h"
 
 #define VJF_CHOL_THREADS 512
 #define VJF_CHOL_MAXBLK 7                 // n <= 224
@@ -677,10 +678,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     if (tid == 0) {
         double t = (double)it_red[P.red_SC + RS_SDX2];
         for (int w = 0; w < VJF_CHOL_THREADS / 64; ++w) t += s_d[w];
-        if (t < 0.0) t = 0.0;
-        const float mse = (float)(t / ((double)Bf * (double)dz));
-        const float acc = fminf(SC[VJF_SC_N_TR], 500.f), tot = acc + Bf;   // running_var, size_cap=500 (model.py:375)
-        S[P.off[VJF_SLOT_TR_LOGVAR]] = logf((acc / tot) * expf(sig) + (Bf / tot) * mse);
+        float tot;
+        S[P.off[VJF_SLOT_TR_LOGVAR]] = vjf_running_logvar(sig, SC[VJF_SC_N_TR], VJF_TR_VAR_CAP, Bf, vjf_resid_mse(t, Bf, dz), tot);
         SC[VJF_SC_N_TR] = tot;
         if (st) vjf_status_or(SC + VJF_SC_STATUS, st);
     }

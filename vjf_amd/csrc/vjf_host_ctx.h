@@ -419,15 +419,15 @@ struct vjf_ctx {
 };
 
 namespace {
-// ---- which kernel an activation uses.  Tanh has kernels of its own (textually separate instantiations: vjf_trial_mfma_kernel.h says
-//      why); every other activation runs the act instantiation, whose signature ends with the VjfAct.  `f` is called with the kernel,
+// ---- which kernel an activation uses.  Tanh has kernels of its own (separate kernels, not a run-time branch: vjf_trial_mfma_body.h
+//      says why); every other activation runs the act instantiation, whose signature ends with the VjfAct.  `f` is called with the kernel,
 //      and with the VjfAct behind it for an act instantiation: f(kernel, tail...) launches with `tail...` as the last arguments.
 template <class KT, class KA, class F>
 auto with_act_kernel(const VjfAct& act, KT tanh_kernel, KA act_kernel, F&& f) {
     if (act.kind == VJF_ACT_TANH) return f(tanh_kernel);
     return f(act_kernel, act);
 }
-template <class F> auto with_trial_kernel(const VjfAct& a, F&& f) { return with_act_kernel(a, vjf_trial_mfma_kernel, vjf_trial_mfma_act_kernel, f); }
+template <class F> auto with_trial_kernel(const VjfAct& a, F&& f) { return with_act_kernel(a, vjf_trial_mfma_kernel<>, vjf_trial_mfma_kernel<VjfAct>, f); }
 template <class F> auto with_mega_kernel(const VjfAct& a, F&& f) { return with_act_kernel(a, vjf_mega_kernel, vjf_mega_act_kernel, f); }
 template <class F> auto with_lite_kernel(const VjfAct& a, F&& f) { return with_act_kernel(a, vjf_mega_lite_kernel, vjf_mega_lite_act_kernel, f); }
 

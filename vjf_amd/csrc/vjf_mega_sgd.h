@@ -22,7 +22,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
     const int n_live = RLS ? A.n_sgd : A.n_sgd_live;
     // a quad of the slab (four consecutive output units of one input: vjf_mega_slab_layout) per 8 lanes: lane p sums the late slabs [p npq, (p+1) npq) (16-byte loads, all in flight together with
     // the quad's old values, its table entries and the step's loss sums), then a fixed xor tree; lane 0 of the group clips and
-    // steps its four parameters (model.py:210-211)
+    // steps its four parameters (vjf_sgd_step)
     const int npq = (A.n_trial + 7) >> 3, part = tid & 7;
     const int nquad = A.slab_len >> 2, qstride = (A.n_sgd * NT) >> 3;
     const int w1 = min(A.n_trial, (part + 1) * npq);
@@ -99,6 +99,8 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
         // loss sums of the step: fp64, 32 strided partial sums per scalar, then a fixed xor tree (every SGD workgroup, for the guards)
         auto take_sums = [&]() {
             mg_sum_losses(A, t, s_sc, tid, Bf, P.dz, do_upd && warm);
+            // (restates vjf_loss_verdict, and below its partial / dropped / status and vjf_put_loss4, vjf_step_math.h: through the
+            //  struct vjf_mega_kernel's lane-spill count rises from 4346 to 5087, profiles/step_math_isa.txt)
             l_recon = s_sc[RS_LRECON] * invB; l_dyn = s_sc[RS_LDYN] * invB; ent = s_sc[RS_ENT] * invB;
             ok_r = isfinite(l_recon); ok_d = isfinite(l_dyn); ok_h = isfinite(ent);
             grad_ok = ok_r && ok_h && (warm || ok_d);
@@ -149,9 +151,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (pidx[r] < 0) continue;                                     // (padding of the slab's rows)
-                float g = vv[r] * invB;
-                g = fminf(fmaxf(g, -1.f), 1.f);                                // clip_grad_value_ (model.py:210)
-                const float wn = wold[r] - (grp == 1 ? lr_dec : lr_rec) * g;
+                const float wn = vjf_sgd_step(wold[r], vv[r], invB, grp == 1 ? lr_dec : lr_rec);
                 wold[r] = wn;
                 if (wst) vjf_st_wt(S + P.train_off + pidx[r], wn);
                 if (cidx[r] >= 0) vjf_st_wt(cdst + cidx[r], wn);
@@ -186,7 +186,7 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
             if (!ok_r) l_recon = 0.f;
             if (!ok_d) l_dyn = 0.f;
             if (!ok_h) ent = 0.f;
-            const float loss = warm ? l_recon - ent : l_recon - ent + l_dyn;      // model.py:146-149
+            const float loss = warm ? l_recon - ent : l_recon - ent + l_dyn;
             if (A.loss) { float* l4 = A.loss + 4 * (size_t)t; l4[0] = loss; l4[1] = -l_recon; l4[2] = -l_dyn; l4[3] = ent; }
             const unsigned st = (ok_r ? 0u : VJF_STATUS_NONFINITE_RECON) | (ok_d ? 0u : VJF_STATUS_NONFINITE_DYN) |
                                 (ok_h ? 0u : VJF_STATUS_NONFINITE_ENT);
@@ -195,28 +195,22 @@ __device__ __forceinline__ void vjf_mega_sgd(const VjfPlan& P, const VjfMegaArgs
                 const float sse_y = s_sc[RS_SSEY];
                 float rho = k_rho;
                 if (do_sgd && ok_r) {                                          // (its gradient comes from the reconstruction term alone)
-                    float g = 0.5f * ((float)P.dy - expf(-rho) * sse_y * invB);
-                    g = fminf(fmaxf(g, -1.f), 1.f);
+                    const float g = vjf_rho_grad(P.dy, rho, sse_y, invB);
                     rho -= SC[VJF_SC_LR_LIK] * g;
                 }
-                if (do_upd) {                                                  // likelihood.py:28-40
+                if (do_upd) {
                     const float mse = sse_y / (Bf * (float)P.dy);
-                    const float acc = fminf(k_nlik, 1000.f), tot = acc + Bf;
-                    rho = logf((acc / tot) * expf(rho) + (Bf / tot) * mse);
-                    k_nlik = tot;
-                    vjf_st_wt(SC + VJF_SC_N_LIK, tot);
+                    rho = vjf_running_logvar(rho, k_nlik, VJF_LIK_VAR_CAP, Bf, mse, k_nlik);
+                    vjf_st_wt(SC + VJF_SC_N_LIK, k_nlik);
                 }
                 k_rho = rho;
                 if (do_sgd || do_upd) vjf_st_wt(S + P.off[VJF_SLOT_LIK_LOGVAR], rho);
             }
             if (do_upd && warm) {
-                // warm-up: no RLS update, the state-noise running variance from the residual with the launch's W (model.py:370-377)
-                const float mse = s_sc[RS_RESID];
-                const float acc = fminf(k_ntr, 500.f), tot = acc + Bf;                            // running_var, size_cap=500 (model.py:375)
-                k_sig = logf((acc / tot) * expf(k_sig) + (Bf / tot) * mse);
-                k_ntr = tot;
+                // warm-up: no RLS update, the state-noise running variance from the residual with the launch's W
+                k_sig = vjf_running_logvar(k_sig, k_ntr, VJF_TR_VAR_CAP, Bf, s_sc[RS_RESID], k_ntr);
                 vjf_st_wt(S + P.off[VJF_SLOT_TR_LOGVAR], k_sig);
-                vjf_st_wt(SC + VJF_SC_N_TR, tot);
+                vjf_st_wt(SC + VJF_SC_N_TR, k_ntr);
             }
         }
         __syncthreads();

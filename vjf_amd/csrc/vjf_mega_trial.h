@@ -643,23 +643,16 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 const int b = tid / LPT, s = tid % LPT;
                 const bool ok = b < nb;
                 float lrec = 0.f, ssey = 0.f;
-                if (P.lik == VJF_LIK_GAUSSIAN) {                               // likelihood.py:19-26, functional.py:54-73
+                if (P.lik == VJF_LIK_GAUSSIAN) {
                     const float p = expf(-0.5f * rho), e = expf(-rho);
                     for (int i = s; i < dy; i += LPT) {
-                        const float yv = s_in[i * LD + b], pv = s_py[i * LD + b];
-                        const float r = pv - yv, dsc = yv * p - pv * p;
-                        lrec += 0.5f * (dsc * dsc + rho);
-                        ssey = fmaf(r, r, ssey);
-                        s_dpy[i * LD + b] = (ok && m_r) ? e * r : 0.f;
+                        const float seed = vjf_gauss_recon(s_in[i * LD + b], s_py[i * LD + b], rho, p, e, lrec, ssey);
+                        s_dpy[i * LD + b] = (ok && m_r) ? seed : 0.f;
                     }
-                } else {                                                       // likelihood.py:51-62
+                } else {
                     for (int i = s; i < dy; i += LPT) {
-                        const float yv = s_in[i * LD + b], pv = s_py[i * LD + b];
-                        const float eta = fminf(pv, 10.f), ex = expf(eta);
-                        lrec += ex - yv * eta;
-                        const float r = pv - yv;
-                        ssey = fmaf(r, r, ssey);
-                        s_dpy[i * LD + b] = (ok && m_r && pv <= 10.f) ? (ex - yv) : 0.f;
+                        const float seed = vjf_poisson_recon(s_in[i * LD + b], s_py[i * LD + b], lrec, ssey);
+                        s_dpy[i * LD + b] = (ok && m_r) ? seed : 0.f;
                     }
                 }
                 lrec = group_sum<LPT>(lrec);
@@ -667,17 +660,11 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 float ldyn = 0.f, ent = 0.f, rsd = 0.f;
                 {
                     const float p = expf(-0.5f * sig), e = expf(-sig), plv = s_plv[b];
-                    for (int j = s; j < dz; j += LPT) {                         // model.py:390-391, functional.py:62-75
-                        const float mp = s_pm[j * LD + b], mu = s_mu[j * LD + b], lv = s_lv[j * LD + b];
+                    for (int j = s; j < dz; j += LPT) {
                         if (want_resid) { const float r = s_dx[j * LD + b] - s_dmu[j * LD + b]; rsd = fmaf(r, r, rsd); }   // (read before dmu goes there)
-                        const float dsc = mp * p - mu * p;
-                        const float tr = expf(plv + lv - sig);
-                        ldyn += 0.5f * (dsc * dsc + sig) + 0.5f * tr;
-                        ent += 0.5f * lv;                                      // functional.py:25-29
-                        float dmu = 0.f, dlv = m_h ? -0.5f : 0.f;
-                        if (!warm && m_d) { dmu = -e * (mp - mu); dlv += 0.5f * tr; }
-                        s_dmu[j * LD + b] = ok ? dmu : 0.f;
-                        s_dlv[j * LD + b] = ok ? dlv : 0.f;
+                        const VjfDynSeed sd = vjf_dyn_term(s_pm[j * LD + b], s_mu[j * LD + b], s_lv[j * LD + b], plv, sig, p, e, !warm && m_d, m_h, ldyn, ent);
+                        s_dmu[j * LD + b] = ok ? sd.dmu : 0.f;
+                        s_dlv[j * LD + b] = ok ? sd.dlv : 0.f;
                     }
                 }
                 ldyn = group_sum<LPT>(ldyn);
@@ -858,16 +845,9 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                         float* s_tot = s_sc;                                   // (the per-trial terms of this workgroup's tile are summed and stored)
                         mg_sum_losses(A, tc, s_tot, tid, (float)A.B, dz, false);
                         if (tid == 0) {
-                            const float invB = 1.0f / (float)A.B;
-                            float l_recon = s_tot[RS_LRECON] * invB, l_dyn = s_tot[RS_LDYN] * invB, ent = s_tot[RS_ENT] * invB;
-                            const bool ok_r = isfinite(l_recon), ok_d = isfinite(l_dyn), ok_h = isfinite(ent);
-                            if (!ok_r) l_recon = 0.f;
-                            if (!ok_d) l_dyn = 0.f;
-                            if (!ok_h) ent = 0.f;
-                            const float loss = warm ? l_recon - ent : l_recon - ent + l_dyn;   // model.py:146-149
-                            if (A.loss) { float* l4 = A.loss + 4 * (size_t)tc; l4[0] = loss; l4[1] = -l_recon; l4[2] = -l_dyn; l4[3] = ent; }
-                            const unsigned st = (ok_r ? 0u : VJF_STATUS_NONFINITE_RECON) | (ok_d ? 0u : VJF_STATUS_NONFINITE_DYN) | (ok_h ? 0u : VJF_STATUS_NONFINITE_ENT);
-                            if (st) vjf_status_or(SCW + VJF_SC_STATUS, st);
+                            const VjfLossVerdict v = vjf_loss_verdict(s_tot[RS_LRECON], s_tot[RS_LDYN], s_tot[RS_ENT], 1.0f / (float)A.B, warm);
+                            if (A.loss) vjf_put_loss4(A.loss + 4 * (size_t)tc, v);
+                            if (v.status()) vjf_status_or(SCW + VJF_SC_STATUS, v.status());
                             __hip_atomic_store(cnt + MG_C_ARR + (tc % VJF_MG_RING), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                             __hip_atomic_fetch_add(cnt + MG_C_SGD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -75,14 +75,13 @@ __global__ __launch_bounds__(256) void vjf_loss_kernel(int mode, const float* m1
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (size_t)VJF_LOSS_BLOCKS * 256) {
         float t;
         if (mode == 0) {
-            const float dsc = m1[i] * p - m2[i] * p;
-            t = 0.5f * (dsc * dsc + lvr);
-            if (lv1 || lv2) t += 0.5f * expf((lv1 ? lv1[i] : 0.f) + (lv2 ? lv2[i] : 0.f) - lvr);
+            t = vjf_gauss_nll(m1[i], m2[i], p, lvr);
+            if (lv1 || lv2) t += 0.5f * expf((lv1 ? lv1[i] : 0.f) + (lv2 ? lv2[i] : 0.f) - lvr);    // (the trace, where either side has a variance)
         } else if (mode == 1) {
-            t = 0.5f * m1[i];
+            t = vjf_entropy_term(m1[i]);
         } else {
-            const float eta = fminf(m1[i], 10.f);
-            t = expf(eta) - m2[i] * eta;
+            const float eta = vjf_poisson_eta(m1[i]);
+            t = vjf_poisson_nll(m2[i], eta, expf(eta));
         }
         acc += (double)t;
     }

@@ -245,9 +245,7 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
         pre_sdx2 = vjf_ld_sc1(it_red + P.red_SC + RS_SDX2);
         const float sig = vjf_ld_sc1(S + P.off[VJF_SLOT_TR_LOGVAR]);
         const float Bf = (float)A.B_total;
-        const float acc = fminf(vjf_ld_sc1(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_N_TR), 500.f);   // running_var, size_cap=500 (model.py:375)
-        pre_tot = acc + Bf;
-        pre_old = (acc / pre_tot) * expf(sig);
+        pre_old = vjf_running_old_share(sig, vjf_ld_sc1(S + P.off[VJF_SLOT_SCALARS] + VJF_SC_N_TR), VJF_TR_VAR_CAP, Bf, pre_tot);
         pre_scale = 1.0 / ((double)Bf * (double)P.dz);
         const float* FDX = it_red + P.red_FDX;
 #pragma unroll
@@ -545,8 +543,8 @@ __device__ __forceinline__ void vjf_rls_post_body(const VjfPlan& P, const VjfPos
             if (t < 0.0) t = 0.0;
             float* St = A.state;
             float* SC = St + P.off[VJF_SLOT_SCALARS];
-            const float mse = (float)(t * pre_scale);
-            const float new_sig = logf(pre_old + ((float)A.B_total / pre_tot) * mse);
+            const float mse = (float)(t * pre_scale);          // (vjf_resid_mse's clamp; a product with the reciprocal formed ahead, not its division)
+            const float new_sig = vjf_running_logvar_split(pre_old, pre_tot, (float)A.B_total, mse);
             if (A.sig_word)                                    // (first: the next step's factorisation waits for this word alone)
                 __hip_atomic_store(A.sig_word, ((unsigned long long)it_epoch << 32) | (unsigned long long)__float_as_uint(new_sig), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -752,12 +750,9 @@ __global__ __launch_bounds__(64) void vjf_sigma_kernel(VjfPlan P, VjfResidArgs A
     float* S = A.state;
     float* SC = S + P.off[VJF_SLOT_SCALARS];
     if (!direct) t += (double)A.red[P.red_SC + RS_SDX2];      // (quadratic form: the partials hold -2 tr(W^T FDX) + tr(W^T G W))
-    if (t < 0.0) t = 0.0;
     const float Bf = (float)A.B_total;
-    const float sig = S[P.off[VJF_SLOT_TR_LOGVAR]];
-    const float mse = (float)(t / ((double)Bf * (double)P.dz));
-    const float acc = fminf(SC[VJF_SC_N_TR], 500.f), tot = acc + Bf;           // running_var, size_cap=500 (model.py:375)
-    S[P.off[VJF_SLOT_TR_LOGVAR]] = logf((acc / tot) * expf(sig) + (Bf / tot) * mse);
+    float tot;
+    S[P.off[VJF_SLOT_TR_LOGVAR]] = vjf_running_logvar(S[P.off[VJF_SLOT_TR_LOGVAR]], SC[VJF_SC_N_TR], VJF_TR_VAR_CAP, Bf, vjf_resid_mse(t, Bf, P.dz), tot);
     SC[VJF_SC_N_TR] = tot;
     if (ok && ok[0] == 0) vjf_status_or(SC + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED);
 }

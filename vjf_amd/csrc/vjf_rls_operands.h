@@ -1,8 +1,8 @@
 // vjf_rls_operands.h -- the many-workgroup kernels in front of the once-per-step serial half (n_rbf <= 224).
 //
 //   vjf_prep_kernel  (many workgroups): everything element-wise that the step's serial half
-//       needs -- finite guards + loss (model.py:138-154), clip + SGD (model.py:210-211),
-//       likelihood running variance (likelihood.py:28-40), g = P W + Phi^T dx / v and
+//       needs -- finite guards + loss, clip + SGD, likelihood running variance
+//       (vjf_step_math.h), g = P W + Phi^T dx / v and
 //       P += Phi^T Phi / v (module.py:94-96) -- so that ONE compute unit is left with nothing
 //       but the dependent chain (vjf_chol_kernel.h).
 //   vjf_prepg_kernel (ceil(n / 16) workgroups): the RLS operands g and P alone, on the matrix cores.
@@ -11,6 +11,7 @@
 #include "vjf_gram_kernel.h"   // vjf_f32x4
 #include "vjf_handoff.h"
 #include "vjf_plan.h"
+#include "vjf_step_math.h"
 
 #define VJF_PREP_ROWS 1                   // rows of P per prep workgroup
 
@@ -49,12 +50,9 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
     const float* RSC = A.red + P.red_SCA;                      // the loss sums (RS_LRECON .. RS_SSEY)
     const bool do_sgd = A.flags & VJF_FLAG_SGD, do_upd = A.flags & VJF_FLAG_UPDATE, warm = A.flags & VJF_FLAG_WARM_UP;
     const float Bf = (float)A.B_total, invB = 1.0f / Bf;
-    float l_recon = RSC[RS_LRECON] * invB, l_dyn = RSC[RS_LDYN] * invB, ent = RSC[RS_ENT] * invB;
-    const bool ok_r = isfinite(l_recon), ok_d = isfinite(l_dyn), ok_h = isfinite(ent);
-    const bool grad_ok = ok_r && ok_h && (warm || ok_d);       // see vjf_serial_kernel / DESIGN.md
-    // some, not all, of the components in the loss are non-finite: the reference steps along the gradient of the others
-    const bool partial = do_sgd && !grad_ok && (ok_r || ok_h || (!warm && ok_d));
-    const bool replay = A.replay_mask != nullptr && partial;
+    const VjfLossVerdict v = vjf_loss_verdict(RSC[RS_LRECON], RSC[RS_LDYN], RSC[RS_ENT], invB, warm);
+    const bool grad_ok = v.grad_ok();
+    const bool replay = A.replay_mask != nullptr && v.partial(do_sgd);
 
     if (bid < A.n_rowblk) {                                    // ---- RLS operands: one row of P per workgroup
         if (!do_upd || warm) return;
@@ -95,9 +93,7 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
             const float lr = P.tr_dec[t] ? lr_dec : lr_rec;
             const int rows = P.tr_rows[t], cols = P.tr_cols[t], off = P.tr_off[t];
             for (int e = g0; e < rows * cols; e += gs) {
-                float g = A.red[off - P.train_off + e] * invB;
-                g = fminf(fmaxf(g, -1.f), 1.f);
-                const float w = S[off + e] - lr * g;
+                const float w = vjf_sgd_step(S[off + e], A.red[off - P.train_off + e], invB, lr);
                 S[off + e] = w;
                 if (P.tr_aux[t] >= 0) {
                     const int r = e / cols, c = e - r * cols;
@@ -111,29 +107,18 @@ __global__ __launch_bounds__(256) void vjf_prep_kernel(VjfPlan P, VjfPrepArgs A)
     if (tid == 0) {                                            // ---- scalars: loss, likelihood log-variance
         if (A.replay_mask) {
             vjf_st_wt(A.replay_rho, S[P.off[VJF_SLOT_LIK_LOGVAR]]);
-            vjf_st_wt(A.replay_mask, replay ? ((ok_r ? 0u : 1u) | (ok_d ? 0u : 2u) | (ok_h ? 0u : 4u)) : 0u);
+            vjf_st_wt(A.replay_mask, replay ? v.dropped() : 0u);
         }
-        if (!ok_r) l_recon = 0.f;
-        if (!ok_d) l_dyn = 0.f;
-        if (!ok_h) ent = 0.f;
-        float loss = l_recon - ent;
-        if (!warm) loss += l_dyn;
-        if (A.loss4) { A.loss4[0] = loss; A.loss4[1] = -l_recon; A.loss4[2] = -l_dyn; A.loss4[3] = ent; }
-        const unsigned st = (ok_r ? 0u : VJF_STATUS_NONFINITE_RECON) | (ok_d ? 0u : VJF_STATUS_NONFINITE_DYN) |
-                            (ok_h ? 0u : VJF_STATUS_NONFINITE_ENT);
-        if (st) vjf_status_or(SC + VJF_SC_STATUS, st);
+        if (A.loss4) vjf_put_loss4(A.loss4, v);
+        if (v.status()) vjf_status_or(SC + VJF_SC_STATUS, v.status());
         if (P.lik == VJF_LIK_GAUSSIAN) {
             const float sse_y = RSC[RS_SSEY];
             float rho = S[P.off[VJF_SLOT_LIK_LOGVAR]];
-            if (do_sgd && (grad_ok || (replay && ok_r))) {       // (its gradient comes from the reconstruction term alone)
-                float g = 0.5f * ((float)P.dy - expf(-rho) * sse_y * invB);
-                g = fminf(fmaxf(g, -1.f), 1.f);
-                rho -= SC[VJF_SC_LR_LIK] * g;
-            }
+            if (do_sgd && (grad_ok || (replay && v.ok_r))) rho -= SC[VJF_SC_LR_LIK] * vjf_rho_grad(P.dy, rho, sse_y, invB);
             if (do_upd) {
                 const float mse = sse_y / (Bf * (float)P.dy);
-                const float acc = fminf(SC[VJF_SC_N_LIK], 1000.f), tot = acc + Bf;
-                rho = logf((acc / tot) * expf(rho) + (Bf / tot) * mse);
+                float tot;
+                rho = vjf_running_logvar(rho, SC[VJF_SC_N_LIK], VJF_LIK_VAR_CAP, Bf, mse, tot);
                 SC[VJF_SC_N_LIK] = tot;
             }
             S[P.off[VJF_SLOT_LIK_LOGVAR]] = rho;

@@ -1,6 +1,7 @@
 // vjf_serial_kernel.h -- K2: the once-per-step serial half of VJF.filter, one workgroup.
 //
 // Consumes the (all-reduced) reduce buffer and applies, in the reference's order:
+// (the scalar formulas themselves: vjf_step_math.h)
 //   finite guards + loss                               model.py:138-154
 //   clip to +-1 and SGD on the optimised tensors       model.py:206-211
 //   likelihood running variance (uses rho AFTER SGD)   likelihood.py:28-40, util.py:20-35
@@ -18,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_plan.h"
+#include "vjf_step_math.h"
 
 #define VJF_K2_THREADS 512
 #define VJF_NB 32
@@ -379,22 +381,16 @@ __global__ __launch_bounds__(VJF_K2_THREADS) void vjf_serial_kernel(VjfPlan P, V
     const bool do_sgd = A.flags & VJF_FLAG_SGD, do_upd = A.flags & VJF_FLAG_UPDATE, warm = A.flags & VJF_FLAG_WARM_UP;
     const float Bf = (float)A.B_total, invB = 1.0f / Bf;
 
-    // ---- losses with the finite guards (model.py:138-149); every thread evaluates the same scalars
-    float l_recon = RSC[RS_LRECON] * invB, l_dyn = RSC[RS_LDYN] * invB, ent = RSC[RS_ENT] * invB;
+    // ---- losses with the finite guards; every thread evaluates the same scalars
+    const VjfLossVerdict v = vjf_loss_verdict(RSC[RS_LRECON], RSC[RS_LDYN], RSC[RS_ENT], invB, warm);
     const float sse_y = RSC[RS_SSEY], sdx2 = A.red[P.red_SC + RS_SDX2];
-    const bool ok_r = isfinite(l_recon), ok_d = isfinite(l_dyn), ok_h = isfinite(ent);
-    if (!ok_r) l_recon = 0.f;
-    if (!ok_d) l_dyn = 0.f;
-    if (!ok_h) ent = 0.f;
-    float loss = l_recon - ent;
-    if (!warm) loss += l_dyn;
-    unsigned st = (ok_r ? 0u : VJF_STATUS_NONFINITE_RECON) | (ok_d ? 0u : VJF_STATUS_NONFINITE_DYN) | (ok_h ? 0u : VJF_STATUS_NONFINITE_ENT);
-    if (tid == 0 && A.loss4) { A.loss4[0] = loss; A.loss4[1] = -l_recon; A.loss4[2] = -l_dyn; A.loss4[3] = ent; }
+    unsigned st = v.status();
+    if (tid == 0 && A.loss4) vjf_put_loss4(A.loss4, v);
     // A non-finite component drops out of the reference's graph; its gradient cannot be separated
     // after the fact, so the SGD step is skipped and the status bit reports it.
-    const bool grad_ok = ok_r && ok_h && (warm || ok_d);
+    const bool grad_ok = v.grad_ok();
 
-    // ---- clip + SGD (model.py:210-211); groups: likelihood, decoder, transition (none), recognition
+    // ---- clip + SGD; groups: likelihood, decoder, transition (none), recognition
     const float lr_lik = SC[VJF_SC_LR_LIK], lr_dec = SC[VJF_SC_LR_DEC], lr_rec = SC[VJF_SC_LR_REC];
     const bool freeze = SC[VJF_SC_FREEZE_DEC] != 0.f;
     float rho = S[P.off[VJF_SLOT_LIK_LOGVAR]];
@@ -406,24 +402,12 @@ __global__ __launch_bounds__(VJF_K2_THREADS) void vjf_serial_kernel(VjfPlan P, V
         for (int i = tid; i < P.train_len; i += VJF_K2_THREADS) {
             const bool dec = i >= dec_rel;
             if (dec && freeze) continue;
-            float g = A.red[i] * invB;
-            g = fminf(fmaxf(g, -1.f), 1.f);
-            S[P.train_off + i] -= (dec ? lr_dec : lr_rec) * g;
+            S[P.train_off + i] = vjf_sgd_step(S[P.train_off + i], A.red[i], invB, dec ? lr_dec : lr_rec);
         }
-        if (P.lik == VJF_LIK_GAUSSIAN) {
-            float g = 0.5f * ((float)P.dy - expf(-rho) * sse_y * invB);
-            g = fminf(fmaxf(g, -1.f), 1.f);
-            rho -= lr_lik * g;
-        }
+        if (P.lik == VJF_LIK_GAUSSIAN) rho -= lr_lik * vjf_rho_grad(P.dy, rho, sse_y, invB);
     }
-    // ---- likelihood running variance (likelihood.py:28-40)
-    if (do_upd && P.lik == VJF_LIK_GAUSSIAN) {
-        const float mse = sse_y / (Bf * (float)P.dy);
-        const float acc = fminf(n_lik, 1000.f), tot = acc + Bf;
-        const float var = (acc / tot) * expf(rho) + (Bf / tot) * mse;
-        rho = logf(var);
-        n_lik = tot;
-    }
+    // ---- likelihood running variance
+    if (do_upd && P.lik == VJF_LIK_GAUSSIAN) rho = vjf_running_logvar(rho, n_lik, VJF_LIK_VAR_CAP, Bf, sse_y / (Bf * (float)P.dy), n_lik);
 
     // ---- transition update (model.py:363-377)
     float* Wm = S + P.off[VJF_SLOT_W_MEAN];
@@ -464,11 +448,8 @@ __global__ __launch_bounds__(VJF_K2_THREADS) void vjf_serial_kernel(VjfPlan P, V
         if (tid == 0) {
             double t = A.E ? 0.0 : (double)sdx2;
             for (int w = 0; w < VJF_K2_THREADS / 64; ++w) t += s_dred[w];
-            if (t < 0.0) t = 0.0;
-            const float mse = (float)(t / ((double)Bf * (double)dz));
-            const float acc = fminf(n_tr, 500.f), tot = acc + Bf;
-            const float var = (acc / tot) * expf(sig) + (Bf / tot) * mse;
-            s_bcast[0] = logf(var);
+            float tot;
+            s_bcast[0] = vjf_running_logvar(sig, n_tr, VJF_TR_VAR_CAP, Bf, vjf_resid_mse(t, Bf, dz), tot);
             s_bcast[1] = tot;
         }
         __syncthreads();

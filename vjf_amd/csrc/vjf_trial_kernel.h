@@ -6,7 +6,7 @@
 //   pt  = (xs + Phi W,  log sum_j (Phi w_chol)_j^2)                    module.py:64-77, model.py:334-340
 //   qt  = Recognition([y,u,mu_s,lv_s])                                 recognition.py:31-42
 //   xt  = mu_t + eps_t * exp(lv_t/2);  py = xt C^T + d                 model.py:119-120, 28-30
-//   per-trial loss terms and the hand-derived backward seeds           model.py:124-154, SURVEY 8a-bwd
+//   per-trial loss terms and the hand-derived backward seeds           model.py:124-154, SURVEY 8a-bwd (vjf_step_math.h)
 // and leaves, for the Gram kernel (K1b), one row per trial of
 //   E = [Phi | xt-xs], ACT = [in|1|h_1|1|..|h_L|1|xt|1], DEL = [da_1|..|da_L|dmu|dlv|dpy]
 // plus per-workgroup partial sums of the loss terms (fixed order => run-to-run deterministic).
@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_plan.h"
+#include "vjf_step_math.h"
 
 #define VJF_K1_THREADS 256
 

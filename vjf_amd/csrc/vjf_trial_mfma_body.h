@@ -1,14 +1,11 @@
-// vjf_trial_mfma_body.h -- the body of the matrix-core trial kernel (vjf_trial_mfma_kernel.h), included twice from there:
-//   VJF_TRIAL_MFMA_ACT 0: vjf_trial_mfma_kernel, the Tanh kernel (tanhf, 1 - h^2);
-//   VJF_TRIAL_MFMA_ACT 1: vjf_trial_mfma_act_kernel, the recognition layers' activation `act` (vjf_act.h; vjf_set_activation).
-// Two textual instantiations rather than one template body behind two kernels: behind a wrapper the Tanh kernel's register
-// allocation changed (64 bytes of scratch per lane where it had none); this way its code is what it was.
-// (no include guard: included once per value of VJF_TRIAL_MFMA_ACT)
-#if VJF_TRIAL_MFMA_ACT
-__global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void vjf_trial_mfma_act_kernel(VjfPlan P, VjfTrialMfmaArgs AA, VjfAct act) {
-#else
-__global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void vjf_trial_mfma_kernel(VjfPlan P, VjfTrialMfmaArgs AA) {
-#endif
+// vjf_trial_mfma_body.h -- the matrix-core trial kernel (included from vjf_trial_mfma_kernel.h, behind what it uses), one template:
+//   vjf_trial_mfma_kernel<>        the Tanh kernel (tanhf, 1 - h^2);
+//   vjf_trial_mfma_kernel<VjfAct>  the recognition layers' activation `act` (vjf_act.h; vjf_set_activation) as a trailing argument.
+// The kernel itself is the template: a template body behind two one-line kernels costs both 64 to 72 bytes of scratch per lane
+// (profiles/step_math_isa.txt); this way their code is what the two textual instantiations gave, instruction for instruction.
+#pragma once
+template <class... ACT>
+__global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void vjf_trial_mfma_kernel(VjfPlan P, VjfTrialMfmaArgs AA, ACT... act) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const VjfTrialArgs& A = AA.t;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -147,11 +144,7 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int f = t * 16 + 4 * (lane >> 4) + r;
-#if VJF_TRIAL_MFMA_ACT
-                    if (f < hl) out[f * LD + (lane & 15)] = vjf_act_fwd(act, acc[r] + bias[f]);
-#else
-                    if (f < hl) out[f * LD + (lane & 15)] = tanhf(acc[r] + bias[f]);
-#endif
+                    if (f < hl) out[f * LD + (lane & 15)] = vjf_k1m_fwd(acc[r] + bias[f], act...);
                 }
             }
             __syncthreads();
@@ -281,23 +274,16 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
         // (sigma may have been written while this kernel was already running: a load that bypasses L1 / the scalar cache)
         const float sig = __hip_atomic_load(S + P.off[VJF_SLOT_TR_LOGVAR], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         float lrec = 0.f, ssey = 0.f;
-        if (P.lik == VJF_LIK_GAUSSIAN) {                               // likelihood.py:19-26, functional.py:54-73
+        if (P.lik == VJF_LIK_GAUSSIAN) {
             const float p = expf(-0.5f * rho), e = expf(-rho);
             for (int i = s; i < dy; i += LPT) {
-                const float yv = s_in[i * LD + b], pv = s_py[i * LD + b];
-                const float r = pv - yv, dsc = yv * p - pv * p;
-                lrec += 0.5f * (dsc * dsc + rho);
-                ssey = fmaf(r, r, ssey);
-                s_dpy[i * LD + b] = m_r ? e * r : 0.f;
+                const float seed = vjf_gauss_recon(s_in[i * LD + b], s_py[i * LD + b], rho, p, e, lrec, ssey);
+                s_dpy[i * LD + b] = m_r ? seed : 0.f;
             }
-        } else {                                                       // likelihood.py:51-62
+        } else {
             for (int i = s; i < dy; i += LPT) {
-                const float yv = s_in[i * LD + b], pv = s_py[i * LD + b];
-                const float eta = fminf(pv, 10.f), ex = expf(eta);
-                lrec += ex - yv * eta;
-                const float r = pv - yv;
-                ssey = fmaf(r, r, ssey);
-                s_dpy[i * LD + b] = (m_r && pv <= 10.f) ? (ex - yv) : 0.f;
+                const float seed = vjf_poisson_recon(s_in[i * LD + b], s_py[i * LD + b], lrec, ssey);
+                s_dpy[i * LD + b] = m_r ? seed : 0.f;
             }
         }
         lrec = group_sum<LPT>(lrec);
@@ -305,18 +291,12 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
         float ldyn = 0.f, ent = 0.f, sdx2 = 0.f;
         {
             const float p = expf(-0.5f * sig), e = expf(-sig), plv = s_plv[b];
-            for (int j = s; j < dz; j += LPT) {                         // model.py:390-391, functional.py:62-75
-                const float mp = s_pm[j * LD + b], mu = s_mu[j * LD + b], lv = s_lv[j * LD + b];
-                const float dsc = mp * p - mu * p;
-                const float tr = expf(plv + lv - sig);
-                ldyn += 0.5f * (dsc * dsc + sig) + 0.5f * tr;
-                ent += 0.5f * lv;                                      // functional.py:25-29
+            for (int j = s; j < dz; j += LPT) {
+                const VjfDynSeed sd = vjf_dyn_term(s_pm[j * LD + b], s_mu[j * LD + b], s_lv[j * LD + b], plv, sig, p, e, !warm && m_d, m_h, ldyn, ent);
                 const float dx = s_xt[j * LD + b] - s_xu[j * LD + b];
                 sdx2 = fmaf(dx, dx, sdx2);
-                float dmu = 0.f, dlv = m_h ? -0.5f : 0.f;
-                if (!warm && m_d) { dmu = -e * (mp - mu); dlv += 0.5f * tr; }
-                s_dmu[j * LD + b] = dmu;
-                s_dlv[j * LD + b] = dlv;
+                s_dmu[j * LD + b] = sd.dmu;
+                s_dlv[j * LD + b] = sd.dlv;
             }
         }
         ldyn = group_sum<LPT>(ldyn);
@@ -370,11 +350,7 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int k = t * 16 + 4 * (lane >> 4) + r, b = lane & 15;
-#if VJF_TRIAL_MFMA_ACT
-                if (k < hL) { const float hv = hact[k * LD + b]; s_d0[k * LD + b] = acc[r] * vjf_act_dh(act, hv); }
-#else
-                if (k < hL) { const float hv = hact[k * LD + b]; s_d0[k * LD + b] = acc[r] * (1.f - hv * hv); }
-#endif
+                if (k < hL) { const float hv = hact[k * LD + b]; s_d0[k * LD + b] = acc[r] * vjf_k1m_dh(hv, act...); }
             }
         }
         __syncthreads();
@@ -397,11 +373,7 @@ __global__ __launch_bounds__(VJF_K1M_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int k = t * 16 + 4 * (lane >> 4) + r, b = lane & 15;
-#if VJF_TRIAL_MFMA_ACT
-                        if (k < hp) { const float hv = hprev[k * LD + b]; nxt[k * LD + b] = acc[r] * vjf_act_dh(act, hv); }
-#else
-                        if (k < hp) { const float hv = hprev[k * LD + b]; nxt[k * LD + b] = acc[r] * (1.f - hv * hv); }
-#endif
+                        if (k < hp) { const float hv = hprev[k * LD + b]; nxt[k * LD + b] = acc[r] * vjf_k1m_dh(hv, act...); }
                     }
                 }
                 __syncthreads();

@@ -114,12 +114,12 @@ static inline size_t vjf_trial_mfma_lds_floats(const VjfPlan& P) {
     return feat * VJF_LDT + 16 * RS_N + VJF_K1M_WAVES * 16 + 16 + 64;
 }
 
-#define VJF_TRIAL_MFMA_ACT 0
-#include "vjf_trial_mfma_body.h"      // vjf_trial_mfma_kernel
-#undef VJF_TRIAL_MFMA_ACT
-#define VJF_TRIAL_MFMA_ACT 1
-#include "vjf_trial_mfma_body.h"      // vjf_trial_mfma_act_kernel
-#undef VJF_TRIAL_MFMA_ACT
+// a hidden layer's activation and its derivative from the layer's output: Tanh without the trailing argument
+__device__ __forceinline__ float vjf_k1m_fwd(float x) { return tanhf(x); }
+__device__ __forceinline__ float vjf_k1m_fwd(float x, const VjfAct& act) { return vjf_act_fwd(act, x); }
+__device__ __forceinline__ float vjf_k1m_dh(float hv) { return 1.f - hv * hv; }
+__device__ __forceinline__ float vjf_k1m_dh(float hv, const VjfAct& act) { return vjf_act_dh(act, hv); }
+#include "vjf_trial_mfma_body.h"      // vjf_trial_mfma_kernel<>, vjf_trial_mfma_kernel<VjfAct>
 
 // Refresh the transposed weight copies from the canonical tensors (run at the start of an API call:
 // the caller may have written the state blob; within a sequence vjf_prep_kernel keeps them in step).

@@ -517,23 +517,16 @@ __global__ __launch_bounds__(256) void vjf_wide_loss_kernel(VjfPlan P, VjfWideAr
         const float* yrow = A.ACT + (size_t)b * P.ldA;            // in = [y | ..]
         const float* py = W.PY + (size_t)b * dy;
         float* drow = A.DEL + (size_t)b * P.ldD;
-        if (P.lik == VJF_LIK_GAUSSIAN) {                       // likelihood.py:19-26, functional.py:54-73
+        if (P.lik == VJF_LIK_GAUSSIAN) {
             const float p = expf(-0.5f * rho), e = expf(-rho);
             for (int i = lane; i < dy; i += 64) {
-                const float yv = yrow[i], pv = py[i];
-                const float r = pv - yv, dsc = yv * p - pv * p;
-                lrec += 0.5f * (dsc * dsc + rho);
-                ssey = fmaf(r, r, ssey);
-                drow[P.colD_dpy + i] = m_r ? e * r : 0.f;
+                const float seed = vjf_gauss_recon(yrow[i], py[i], rho, p, e, lrec, ssey);
+                drow[P.colD_dpy + i] = m_r ? seed : 0.f;
             }
-        } else {                                               // likelihood.py:51-62
+        } else {
             for (int i = lane; i < dy; i += 64) {
-                const float yv = yrow[i], pv = py[i];
-                const float eta = fminf(pv, 10.f), ex = expf(eta);
-                lrec += ex - yv * eta;
-                const float r = pv - yv;
-                ssey = fmaf(r, r, ssey);
-                drow[P.colD_dpy + i] = (m_r && pv <= 10.f) ? (ex - yv) : 0.f;
+                const float seed = vjf_poisson_recon(yrow[i], py[i], lrec, ssey);
+                drow[P.colD_dpy + i] = m_r ? seed : 0.f;
             }
         }
         float zz = 0.f;                                        // pt.logvar = log sum_j Z[b][j]^2 (module.py:76), fixed-order lane sums
@@ -541,18 +534,13 @@ __global__ __launch_bounds__(256) void vjf_wide_loss_kernel(VjfPlan P, VjfWideAr
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) zz += __shfl_xor(zz, o, 64);
         const float p = expf(-0.5f * sig), e = expf(-sig), plv = logf(zz);
-        for (int j = lane; j < dz; j += 64) {                  // model.py:390-391, functional.py:62-75
-            const float mp = W.PM[(size_t)b * dz + j], mu = A.mu_t[(size_t)b * dz + j], lv = A.lv_t[(size_t)b * dz + j];
-            const float dsc = mp * p - mu * p;
-            const float tr = expf(plv + lv - sig);
-            ldyn += 0.5f * (dsc * dsc + sig) + 0.5f * tr;
-            ent += 0.5f * lv;                                  // functional.py:25-29
+        for (int j = lane; j < dz; j += 64) {
+            const VjfDynSeed sd = vjf_dyn_term(W.PM[(size_t)b * dz + j], A.mu_t[(size_t)b * dz + j], A.lv_t[(size_t)b * dz + j], plv, sig, p, e,
+                                               !warm && m_d, m_h, ldyn, ent);
             const float dx = A.E[(size_t)b * P.ldE + P.n + j];
             sdx2 = fmaf(dx, dx, sdx2);
-            float dmu = 0.f, dlv = m_h ? -0.5f : 0.f;
-            if (!warm && m_d) { dmu = -e * (mp - mu); dlv += 0.5f * tr; }
-            drow[P.colD_dmu + j] = dmu;                        // the decoder path is added by the dxt GEMM's epilogue
-            drow[P.colD_dlv + j] = dlv;
+            drow[P.colD_dmu + j] = sd.dmu;                     // the decoder path is added by the dxt GEMM's epilogue
+            drow[P.colD_dlv + j] = sd.dlv;
         }
     }
 #pragma unroll
