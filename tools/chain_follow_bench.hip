@@ -9,7 +9,7 @@
 #define NREP 12
 __global__ __launch_bounds__(128) void k(const float* A, const float* Pn, const float* Nn, float* out, unsigned long long* t, int mode, int delay) {
     extern __shared__ float lds[];                     // (dynamic, carved by offsets as the product does)
-    float* blk = lds; float* inv = blk + 1024; float* pan = inv + 1024; float* nxt = pan + 1024; float* ring = nxt + 1024; float* rsc = ring + 1024;
+    float* blk = lds; float* inv = blk + VJF_BLK_FLOATS; float* pan = inv + VJF_BLK_FLOATS; float* nxt = pan + VJF_BLK_FLOATS; float* ring = nxt + VJF_BLK_FLOATS; float* rsc = ring + VJF_BLK_FLOATS;
     volatile int* rnd = (volatile int*)(rsc + 48);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool ok = true;
@@ -59,7 +59,7 @@ int main() {
     auto mn = [&](int q) { unsigned long long m = ~0ull; for (int r = 2; r < NREP; ++r) m = h[2 * r + q] < m ? h[2 * r + q] : m; return m; };
     auto run = [&](const char* name, int mode, int delay) {
         (void)hipMemset(t, 0, 16 * NREP);
-        k<<<1, 128, (5 * 1024 + 64) * 4>>>(dA, dP, dN, out, t, mode, delay);
+        k<<<1, 128, (5 * VJF_BLK_FLOATS + 64) * 4>>>(dA, dP, dN, out, t, mode, delay);
         (void)hipMemcpy(h, t, sizeof h, hipMemcpyDeviceToHost); (void)hipMemcpy(ho, out, sizeof ho, hipMemcpyDeviceToHost);
         double eL = 0, eI = 0, eX = 0, eN = 0;
         for (int r = 0; r < 32; ++r) for (int c = 0; c < 32; ++c) {

@@ -11,7 +11,7 @@ __global__ void spin(float* out, int n) {
     if (v == 123.f) out[0] = v;
 }
 __global__ __launch_bounds__(64) void longrun(const float* A, float* out, unsigned long long* t, int n) {
-    __shared__ float blk[1024], piv[32], src[1024];
+    __shared__ float blk[VJF_BLK_FLOATS], piv[32], src[VJF_BLK_FLOATS];
     const int lane = threadIdx.x & 63;
     for (int e = threadIdx.x; e < 1024; e += blockDim.x) { int r = e >> 5, c = e & 31; src[vsw(r, c)] = A[e]; }
     __syncthreads();
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) void longrun(const float* A, float* out, unsign
 #define NREP 12
 template <int VAR>
 __global__ __launch_bounds__(64) void k(const float* A, const float* Pn, float* out, unsigned long long* t) {
-    __shared__ float blk[1024], inv[1024], pan[1024], piv[32];
+    __shared__ float blk[VJF_BLK_FLOATS], inv[VJF_BLK_FLOATS], pan[VJF_BLK_FLOATS], piv[32];
     const int lane = threadIdx.x & 63;
     bool ok = true;
     for (int rep = 0; rep < NREP; ++rep) {

@@ -6,9 +6,16 @@
 #include "vjf_gram_kernel.h"   // vjf_f32x16
 
 // ---------------------------------------------------------------------------------------------
-// LDS block helpers.  A 32x32 block is 1024 floats; element (r,c) sits at r*32 + (c ^ r), which
-// makes row reads, column reads and the MFMA operand reads bank-conflict free.
-__device__ __forceinline__ int vsw(int r, int c) { return r * 32 + (c ^ r); }
+// LDS block helpers.  A 32x32 block is 32 rows of VJF_BLK_LD = 33 floats in LDS; element (r,c) sits at r*33 + c.  Every
+// block access is a dword access (bank = dword address mod 32, conflicts only inside a half-wavefront), and the patterns in
+// use -- c*33 + m, m*33 + c, row*33 + c over the lanes c, the chain's lc*33 + j / j*33 + lc (lc a permutation of the lane) and
+// the intake's r*33 + c4 + i (four rows x eight quads) -- put 32 lanes on 32 banks.  Unlike an XOR swizzle, which folds the
+// lane into every element offset, each access of a product is ONE per-lane base plus a compile-time offset (the instruction's
+// immediate): the routines below form that base once.  Rows are not 16-byte aligned: no wider access to a block.  The last
+// float of a block (VJF_BLK_FLOATS - 1) belongs to no element.  Blocks in GLOBAL memory stay 1024 floats, row-major.
+#define VJF_BLK_LD 33
+#define VJF_BLK_FLOATS (32 * VJF_BLK_LD)
+__device__ __forceinline__ int vsw(int r, int c) { return r * VJF_BLK_LD + c; }
 __device__ __forceinline__ int vtri(int bi, int bj) { return bi * (bi + 1) / 2 + bj; }
 // accumulator layout of v_mfma_f32_32x32x2_f32: column = lane & 31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
 __device__ __forceinline__ int vrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
@@ -22,41 +29,42 @@ __device__ __forceinline__ float vrsqrt(float d) {               // rsqrt with o
 }
 
 __device__ __forceinline__ void blk_load(vjf_f32x16& acc, const float* blk, int lane) {
-    const int c = lane & 31, h = lane >> 5;
+    const float* p = blk + vsw(4 * (lane >> 5), lane & 31);       // row vrow(r, h) = vrow(r, 0) + 4 h
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = blk[vsw(vrow(r, h), c)];
+    for (int r = 0; r < 16; ++r) acc[r] = p[vrow(r, 0) * VJF_BLK_LD];
 }
 __device__ __forceinline__ void blk_store(const vjf_f32x16& acc, float* blk, int lane) {
-    const int c = lane & 31, h = lane >> 5;
+    float* p = blk + vsw(4 * (lane >> 5), lane & 31);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) blk[vsw(vrow(r, h), c)] = acc[r];
+    for (int r = 0; r < 16; ++r) p[vrow(r, 0) * VJF_BLK_LD] = acc[r];
 }
-// acc += sign * Ab * Bb      (Bt: use Bb^T)
-template <bool Bt>
-__device__ __forceinline__ void blk_mma(vjf_f32x16& acc, const float* Ab, const float* Bb, float sign, int lane) {
+// acc += Ab * Bb  (Neg: acc -= Ab * Bb; Bt: use Bb^T).  MFMA step t takes k = 2 t + h: A[c][k] and B[k][c] (Bt: B[c][k])
+template <bool Bt, bool Neg = false>
+__device__ __forceinline__ void blk_mma(vjf_f32x16& acc, const float* Ab, const float* Bb, int lane) {
     const int c = lane & 31, h = lane >> 5;
+    const float* pa = Ab + vsw(c, h);
+    const float* pb = Bb + (Bt ? vsw(c, h) : vsw(h, c));
     float a[16], b[16];
 #pragma unroll
     for (int t = 0; t < 16; ++t) {                   // all 32 operand reads first ...
-        const int m = 2 * t + h;
-        a[t] = Ab[vsw(c, m)];
-        b[t] = Bt ? Bb[vsw(c, m)] : Bb[vsw(m, c)];
+        a[t] = pa[2 * t];
+        b[t] = pb[Bt ? 2 * t : 2 * t * VJF_BLK_LD];
     }
     __builtin_amdgcn_sched_barrier(0);               // ... so the 16 MFMAs issue back to back
 #pragma unroll
-    for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sign * a[t], b[t], acc, 0, 0, 0);
+    for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Neg ? -a[t] : a[t], b[t], acc, 0, 0, 0);
 }
 
-// acc += A * B with operands given by functors: fa(i, m) = A[i][m], fb(m, j) = B[m][j]  (i, j = lane & 31)
-template <class FA, class FB>
-__device__ __forceinline__ void blk_mma_f(vjf_f32x16& acc, int lane, FA fa, FB fb) {
+// acc += A * B with A a block in LDS (At: its transpose) and B given by a functor: fb(m, j) = B[m][j]  (j = lane & 31)
+template <bool At, class FB>
+__device__ __forceinline__ void blk_mma_f(vjf_f32x16& acc, int lane, const float* Ab, FB fb) {
     const int c = lane & 31, h = lane >> 5;
+    const float* pa = Ab + (At ? vsw(h, c) : vsw(c, h));
     float a[16], b[16];
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
-        const int m = 2 * t + h;
-        a[t] = fa(c, m);
-        b[t] = fb(m, c);
+        a[t] = pa[At ? 2 * t * VJF_BLK_LD : 2 * t];
+        b[t] = fb(2 * t + h, c);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -82,10 +90,11 @@ __device__ __forceinline__ bool potrf_inv_chain2(float* dk, float* inv, int lane
     const int c = lane & 31, h = lane >> 5;
     const int lc = 2 * ((c & 3) + 4 * (c >> 3)) + ((c >> 2) & 1);   // logical column held by this lane
     vjf_f32x16 acc, racc;
+    const float* pin = dk + vsw(h, lc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int lr = 2 * r + h;                                   // logical row of (register r, half h)
-        acc[r] = dk[vsw(lr, lc)];
+        acc[r] = pin[2 * r * VJF_BLK_LD];
         racc[r] = (lr == lc) ? 1.f : 0.f;
     }
     float vcol[16], xcol[16];
@@ -117,11 +126,13 @@ __device__ __forceinline__ bool potrf_inv_chain2(float* dk, float* inv, int lane
         racc = __builtin_amdgcn_mfma_f32_32x32x2f32(nv, b, racc, 0, 0, 0);
         }
     }
+    float* pl = dk + vsw(lc, h);
+    float* px = inv + vsw(h, lc);
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
         const int j = 2 * m + h;
-        if (lc >= j) dk[vsw(lc, j)] = vcol[m];
-        inv[vsw(j, lc)] = (lc <= j) ? xcol[m] : 0.f;
+        if (lc >= j) pl[2 * m] = vcol[m];                           // dk[vsw(lc, j)]
+        px[2 * m * VJF_BLK_LD] = (lc <= j) ? xcol[m] : 0.f;         // inv[vsw(j, lc)]
     }
     return (dmin > 0.f) && (slast == slast) && (fabsf(slast) < 3.0e38f);
 }

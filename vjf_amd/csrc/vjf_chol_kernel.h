@@ -2,8 +2,8 @@
 //
 //   vjf_chol_lds_kernel (one workgroup, 8 wavefronts): L = chol(P) (module.py:99),
 //       W = P^-1 g (module.py:101), w_chol = L^-T (module.py:102), residual -> state-noise
-//       running variance (model.py:373-377).  The matrix lives in LDS as XOR-swizzled 32x32
-//       blocks; all block products run on the f32 matrix cores (v_mfma_f32_32x32x2_f32).
+//       running variance (model.py:373-377).  The matrix lives in LDS as 32x32 blocks with
+//       33-float rows; all block products run on the f32 matrix cores (v_mfma_f32_32x32x2_f32).
 //       The two column-sequential pieces (diagonal-block Cholesky, triangular block solve) are
 //       written as chains of rank-1 MFMA updates on an accumulator tile: the symmetric tile has
 //       row j already spread over the lanes (column index on the lane), which is exactly the
@@ -66,10 +66,15 @@ struct VjfCholArgs {
     } while (0)
 
 static inline int vjf_chol_dzp(int dz) { return dz <= 4 ? 4 : dz <= 8 ? 8 : dz <= 12 ? 12 : dz <= 16 ? 16 : 32; }
+// The control words behind s_g: [0] ok, [2] [3] sigma's bits / "there", [4..13] the column loop's hand-off words, [16..31] eight
+// doubles of the final reduction.  (The block-row / block-column table of the lower blocks needs no room here: entry b sits in
+// the one float of block b that belongs to no element.)  With 32 floats the largest plans keep the sizes they had with
+// 1024-float blocks and 192 control floats within the same budget: nbl = 6, dzp = 32 is 163,328 B, the bound itself.
+#define VJF_CHOL_CTL_FLOATS 32
 static inline size_t vjf_chol_lds_bytes(const VjfPlan& P, int dzp) {            // dynamic LDS of vjf_chol_loop<dzp>
     const int nbl = (P.n + 31) / 32;
-    const size_t blocks = (size_t)(nbl * (nbl + 1) / 2 + nbl) * 1024;
-    return (blocks + (size_t)nbl * 32 * dzp * (dzp <= 16 ? 1 : 2) + 192) * 4;   // dzp = 32: y = L^-1 g has a region of its own
+    const size_t blocks = (size_t)(nbl * (nbl + 1) / 2 + nbl) * VJF_BLK_FLOATS;
+    return (blocks + (size_t)nbl * 32 * dzp * (dzp <= 16 ? 1 : 2) + VJF_CHOL_CTL_FLOATS) * 4;   // dzp = 32: y = L^-1 g has a region of its own
 }
 static inline size_t vjf_chol_lds_bytes(const VjfPlan& P) { return vjf_chol_lds_bytes(P, vjf_chol_dzp(P.dz)); }
 static inline bool vjf_chol_lds_ok(const VjfPlan& P) {
@@ -124,13 +129,13 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     //  state's P, starts behind a gate on it)
     if (A.post && !A.self_prep && tid == 0) vjf_st_wt(A.flags_out + VJF_CHOL_MAXBLK + 2, it_epoch);
     float* s_blk = lds;                               // ntri blocks: lower block triangle of P -> L -> L^-1
-    float* s_aux = s_blk + (size_t)ntri * 1024;       // nbl blocks: inverted diagonal blocks of L; later scratch
-    float* s_g = s_aux + (size_t)nbl * 1024;          // npad x DZP  g, later W
+    float* s_aux = s_blk + (size_t)ntri * VJF_BLK_FLOATS;       // nbl blocks: inverted diagonal blocks of L; later scratch
+    float* s_g = s_aux + (size_t)nbl * VJF_BLK_FLOATS;          // npad x DZP  g, later W
     // (y = L^-1 g overwrites g in place; for DZP = 32 a second npad x DZP region behind g is reserved)
     int* s_flag = (int*)(s_g + (size_t)npad * DZP * (DZP <= 16 ? 1 : 2));   // [0] ok
-    double* s_d = (double*)(s_flag + 8);              // 16 doubles for the final reduction
-    int* s_bi = s_flag + 64;                          // block-row / block-column of lower block b
-    int* s_bj = s_bi + 32;
+    double* s_d = (double*)(s_flag + 16);             // 8 doubles for the final reduction (one per wavefront)
+    int* s_tab = (int*)s_blk + (VJF_BLK_FLOATS - 1);  // s_tab[b * VJF_BLK_FLOATS]: first row << 16 | first column of lower block b
+    auto tile_at = [&](int b, int& gi0, int& gj0) { const int v = s_tab[(size_t)b * VJF_BLK_FLOATS]; gi0 = v >> 16; gj0 = v & 0xffff; };
 
     float* Wm = S + P.off[VJF_SLOT_W_MEAN];
     float* Wc = S + P.off[VJF_SLOT_W_CHOL];
@@ -144,14 +149,17 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
     unsigned st = 0;
     const bool sp = A.post && A.self_prep;
     VJF_STAMP(0);
-    if (tid < ntri) {
-        int bi = 0;
-        while ((bi + 1) * (bi + 2) / 2 <= tid) ++bi;
-        s_bi[tid] = bi;
-        s_bj[tid] = tid - bi * (bi + 1) / 2;
-    }
+    // (the entries of the table sit in ONE bank, VJF_BLK_FLOATS % 32 == 0: 28 lanes of a wavefront storing them was a 28-way
+    //  conflict; lane 0 of every wavefront stores its <= 4 entries one after the other instead.  Readers of an entry are the
+    //  lanes of one wavefront with the same b: a broadcast)
+    if (lane == 0)
+        for (int b = wave; b < ntri; b += VJF_CHOL_THREADS / 64) {
+            int bi = 0;
+            while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;
+            s_tab[(size_t)b * VJF_BLK_FLOATS] = (bi * 32) << 16 | (b - bi * (bi + 1) / 2) * 32;
+        }
     if (tid == 0) s_flag[0] = 1;
-    if (tid < 16) s_flag[128 + tid] = 0;                // the column loop's hand-off words (below)
+    if (tid < 10) s_flag[4 + tid] = 0;                  // the column loop's hand-off words (below)
     __syncthreads();
     // (the statistics of the step: the Gram role's write-through stores, read with sc1 loads behind their count -- an acquire as
     //  well only in the VJF_HANDOFF_ACQUIRE=1 form.  The wait sits below, between this thread's loads of P, which do not depend on
@@ -174,8 +182,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         //      first diagonal block alone and starts its column chain; the other seven bring in the rest meanwhile.
         //      All loads of a thread are issued before its first LDS store.
         auto diag_chain = [&](int k) {                                  // L_kk and L_kk^-1 in one chain (one wavefront)
-            float* dk = s_blk + (size_t)vtri(k, k) * 1024;
-            const bool good = potrf_inv_chain2(dk, s_aux + (size_t)k * 1024, lane, min(32, n - 32 * k));
+            float* dk = s_blk + (size_t)vtri(k, k) * VJF_BLK_FLOATS;
+            const bool good = potrf_inv_chain2(dk, s_aux + (size_t)k * VJF_BLK_FLOATS, lane, min(32, n - 32 * k));
             if (!good && lane == 0) s_flag[0] = 0;
             return good;
         };
@@ -232,7 +240,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             v[q] = make_float4(0.f, 0.f, 0.f, 0.f); g[q] = v[q];
             if (idx < ntri * 256) {
                 int b, r, c4; chol_tile_of(idx, b, r, c4);
-                const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
+                int gi, gj; tile_at(b, gi, gj); gi += r; gj += c4;
                 if (sp && !it_src_state) v[q] = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);
                 else v[q] = (gi < n && gj < n) ? *reinterpret_cast<const float4*>(Pm + (size_t)gi * n + gj) : pad4(gi, gj);
             }
@@ -244,7 +252,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                 const int idx = idx_of(q);
                 if (idx < ntri * 256) {
                     int b, r, c4; chol_tile_of(idx, b, r, c4);
-                    g[q] = g4(s_bi[b] * 32 + r, s_bj[b] * 32 + c4);
+                    int gi, gj; tile_at(b, gi, gj);
+                    g[q] = g4(gi + r, gj + c4);
                 }
             }
         }
@@ -265,8 +274,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             const int idx = idx_of(q);
             if (idx < ntri * 256) {
                 int b, r, c4; chol_tile_of(idx, b, r, c4);
-                float* blk = s_blk + (size_t)b * 1024;
-                blk[vsw(r, c4)] = v[q].x; blk[vsw(r, c4 + 1)] = v[q].y; blk[vsw(r, c4 + 2)] = v[q].z; blk[vsw(r, c4 + 3)] = v[q].w;
+                float* p = s_blk + (size_t)b * VJF_BLK_FLOATS + vsw(r, c4);   // (four dword stores: a row is not 16-byte aligned)
+                p[0] = v[q].x; p[1] = v[q].y; p[2] = v[q].z; p[3] = v[q].w;
                 if (A.post) *reinterpret_cast<float4*>(A.pscr + (size_t)idx * 4) = v[q];
             }
         }
@@ -289,11 +298,12 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int idx = lane + 64 * q, r = idx >> 3, c4 = (idx & 7) * 4;
+                const float* p = blk + vsw(r, c4);
                 vjf_f32x4 o;
-                o[0] = (!lower_only || c4 <= r) ? blk[vsw(r, c4)] : 0.f;
-                o[1] = (!lower_only || c4 + 1 <= r) ? blk[vsw(r, c4 + 1)] : 0.f;
-                o[2] = (!lower_only || c4 + 2 <= r) ? blk[vsw(r, c4 + 2)] : 0.f;
-                o[3] = (!lower_only || c4 + 3 <= r) ? blk[vsw(r, c4 + 3)] : 0.f;
+                o[0] = (!lower_only || c4 <= r) ? p[0] : 0.f;
+                o[1] = (!lower_only || c4 + 1 <= r) ? p[1] : 0.f;
+                o[2] = (!lower_only || c4 + 2 <= r) ? p[2] : 0.f;
+                o[3] = (!lower_only || c4 + 3 <= r) ? p[3] : 0.f;
                 if (gi0 + r < ld && gj0 + c4 < ld) vjf_st4_wt(dst + (size_t)(gi0 + r) * ld + gj0 + c4, o);
             }
         };
@@ -315,7 +325,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
         //        c_hb[h]  = stages helper h has completed: stage s is complete when every c_hb[h] > s
         //      Every update of a tile is applied in column order by construction (stage barriers), so the bits do not depend on
         //      timing.  Polls are bounded: a logic error shows as a failed factorisation, not as a hang.
-        volatile int* s_ctl = s_flag + 128;
+        volatile int* s_ctl = s_flag + 4;                              // C_HB + 6 = 10 words
         enum { C_CHAIN = 0, C_P1 = 1, C_A = 2, C_B = 3, C_HB = 4 };
         volatile int* v_ok = s_flag;                                   // [0]: 1 while every pivot was positive (wavefront 0 clears it)
         auto lds_wait = [&](int w, int target) {                       // one wavefront: all lanes poll the same word
@@ -345,18 +355,18 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         };
         auto panel_tile = [&](int bi, int k) {                         // L_ik = A_ik Dinv_k^T, in place (one wavefront reads all of it first)
-            float* pb = s_blk + (size_t)vtri(bi, k) * 1024;
+            float* pb = s_blk + (size_t)vtri(bi, k) * VJF_BLK_FLOATS;
             vjf_f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            blk_mma<true>(acc, pb, s_aux + (size_t)k * 1024, 1.f, lane);
+            blk_mma<true>(acc, pb, s_aux + (size_t)k * VJF_BLK_FLOATS, lane);
             blk_store(acc, pb, lane);
         };
         auto trail_tile = [&](int bi, int bj, int k) {                 // A_ij -= L_ik L_jk^T
-            float* cb = s_blk + (size_t)vtri(bi, bj) * 1024;
+            float* cb = s_blk + (size_t)vtri(bi, bj) * VJF_BLK_FLOATS;
             vjf_f32x16 acc;
             blk_load(acc, cb, lane);
-            blk_mma<true>(acc, s_blk + (size_t)vtri(bi, k) * 1024, s_blk + (size_t)vtri(bj, k) * 1024, -1.f, lane);
+            blk_mma<true, true>(acc, s_blk + (size_t)vtri(bi, k) * VJF_BLK_FLOATS, s_blk + (size_t)vtri(bj, k) * VJF_BLK_FLOATS, lane);
             blk_store(acc, cb, lane);
         };
         int kdone = 0;                                                  // wavefront 4: columns written out (their flags stored)
@@ -406,8 +416,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                         }
                         if (!there && lane == 0) { vjf_status_or(SC + VJF_SC_STATUS, VJF_STATUS_RLS_FAILED | VJF_STATUS_WAIT_SIGMA); *s_dead = 1; }
                     }
-                    for (int it = 0; it < nbl - k; ++it) put_block(s_blk + (size_t)vtri(k + it, k) * 1024, A.lscr, n, (k + it) * 32, k * 32, it == 0);
-                    put_block(s_aux + (size_t)k * 1024, A.dinv_out + (size_t)k * 1024, 32, 0, 0, false);
+                    for (int it = 0; it < nbl - k; ++it) put_block(s_blk + (size_t)vtri(k + it, k) * VJF_BLK_FLOATS, A.lscr, n, (k + it) * 32, k * 32, it == 0);
+                    put_block(s_aux + (size_t)k * VJF_BLK_FLOATS, A.dinv_out + (size_t)k * 1024, 32, 0, 0, false);
                     publish(k, k + 1, 0u);
                     kdone = k + 1;
                 }
@@ -452,7 +462,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             if (A.post) {
                 for (int idx = tid; idx < ntri * 256; idx += VJF_CHOL_THREADS) {   // the copy for the next kernel, likewise
                     int b, r, c4; chol_tile_of(idx, b, r, c4);
-                    const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
+                    int gi, gj; tile_at(b, gi, gj); gi += r; gj += c4;
                     if (gi < n && gj < n) {
                         float4 pv = *reinterpret_cast<const float4*>(A.pscr + (size_t)idx * 4);
                         const float4 gv = g4(gi, gj);          // (another role's stores on the one-launch route: an sc1 load there, found by tools/audit_plain_loads.py)
@@ -487,12 +497,13 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
                         int b, r, c4; chol_tile_of(idx, b, r, c4);
-                        const float* blk = s_blk + (size_t)b * 1024;
-                        const bool dg = s_bi[b] == s_bj[b];
-                        v[q].x = (!dg || c4 <= r) ? blk[vsw(r, c4)] : 0.f;
-                        v[q].y = (!dg || c4 + 1 <= r) ? blk[vsw(r, c4 + 1)] : 0.f;
-                        v[q].z = (!dg || c4 + 2 <= r) ? blk[vsw(r, c4 + 2)] : 0.f;
-                        v[q].w = (!dg || c4 + 3 <= r) ? blk[vsw(r, c4 + 3)] : 0.f;
+                        const float* p = s_blk + (size_t)b * VJF_BLK_FLOATS + vsw(r, c4);
+                        int gi0, gj0; tile_at(b, gi0, gj0);
+                        const bool dg = gi0 == gj0;
+                        v[q].x = (!dg || c4 <= r) ? p[0] : 0.f;
+                        v[q].y = (!dg || c4 + 1 <= r) ? p[1] : 0.f;
+                        v[q].z = (!dg || c4 + 2 <= r) ? p[2] : 0.f;
+                        v[q].w = (!dg || c4 + 3 <= r) ? p[3] : 0.f;
                     }
                 }
 #pragma unroll
@@ -500,7 +511,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
                         int b, r, c4; chol_tile_of(idx, b, r, c4);
-                        const int gi = s_bi[b] * 32 + r, gj = s_bj[b] * 32 + c4;
+                        int gi, gj; tile_at(b, gi, gj); gi += r; gj += c4;
                         if (gi < n && gj < n) *reinterpret_cast<float4*>(Lm + (size_t)gi * n + gj) = v[q];
                     }
                 }
@@ -517,29 +528,32 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
 #pragma unroll
                     for (int r = 0; r < 16; ++r) t[r] = 0.f;
                     for (int k = bj; k < bi; ++k) {
-                        const float* xb = (k == bj) ? s_aux + (size_t)bj * 1024 : s_blk + (size_t)vtri(k, bj) * 1024;
-                        blk_mma<false>(t, s_blk + (size_t)vtri(bi, k) * 1024, xb, 1.f, lane);
+                        const float* xb = (k == bj) ? s_aux + (size_t)bj * VJF_BLK_FLOATS : s_blk + (size_t)vtri(k, bj) * VJF_BLK_FLOATS;
+                        blk_mma<false>(t, s_blk + (size_t)vtri(bi, k) * VJF_BLK_FLOATS, xb, lane);
                     }
                     // X_ij = -Dinv_i * T with T taken straight from the accumulator: register r of T holds
                     // rows vrow(r,0) / vrow(r,1) on the two lane halves = the k pair of MFMA step r.
-                    const float* di = s_aux + (size_t)bi * 1024;
-                    const int c = lane & 31, h = lane >> 5;
+                    const float* di = s_aux + (size_t)bi * VJF_BLK_FLOATS + vsw(lane & 31, 4 * (lane >> 5));
 #pragma unroll
                     for (int r = 0; r < 16; ++r) xacc[r] = 0.f;
                     float da[16];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) da[r] = -di[vsw(c, vrow(r, h))];
+                    for (int r = 0; r < 16; ++r) da[r] = -di[vrow(r, 0)];          // Dinv_i[c][vrow(r, h)]
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) xacc = __builtin_amdgcn_mfma_f32_32x32x2f32(da[r], t[r], xacc, 0, 0, 0);
                 }
                 __syncthreads();                                       // every reader of row bi of L is done
-                if (bj < bi) blk_store(xacc, s_blk + (size_t)vtri(bi, bj) * 1024, lane);
+                if (bj < bi) blk_store(xacc, s_blk + (size_t)vtri(bi, bj) * VJF_BLK_FLOATS, lane);
                 __syncthreads();
             }
             VJF_STAMP(5);
             // diagonal blocks of X
-            for (int e = tid; e < nbl * 1024; e += VJF_CHOL_THREADS) s_blk[(size_t)vtri(e >> 10, e >> 10) * 1024 + (e & 1023)] = s_aux[e];
+            // (element by element: the last float of a block of s_blk is its entry of the tile table)
+            for (int e = tid; e < nbl * 1024; e += VJF_CHOL_THREADS) {
+                const int o = vsw((e >> 5) & 31, e & 31);
+                s_blk[(size_t)vtri(e >> 10, e >> 10) * VJF_BLK_FLOATS + o] = s_aux[(size_t)(e >> 10) * VJF_BLK_FLOATS + o];
+            }
             __syncthreads();
             // ---- w_chol = X^T (upper, module.py:102): row (bj*32+c) of w_chol, 4 consecutive r per store
             {
@@ -549,12 +563,13 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
                         int b, c, r4; chol_tile_of(idx, b, c, r4);
-                        const float* blk = s_blk + (size_t)b * 1024;
-                        const bool dg = s_bi[b] == s_bj[b];
-                        v[q].x = (!dg || c <= r4) ? blk[vsw(r4, c)] : 0.f;
-                        v[q].y = (!dg || c <= r4 + 1) ? blk[vsw(r4 + 1, c)] : 0.f;
-                        v[q].z = (!dg || c <= r4 + 2) ? blk[vsw(r4 + 2, c)] : 0.f;
-                        v[q].w = (!dg || c <= r4 + 3) ? blk[vsw(r4 + 3, c)] : 0.f;
+                        const float* p = s_blk + (size_t)b * VJF_BLK_FLOATS + vsw(r4, c);
+                        int gi0, gj0; tile_at(b, gi0, gj0);
+                        const bool dg = gi0 == gj0;
+                        v[q].x = (!dg || c <= r4) ? p[0] : 0.f;
+                        v[q].y = (!dg || c <= r4 + 1) ? p[VJF_BLK_LD] : 0.f;
+                        v[q].z = (!dg || c <= r4 + 2) ? p[2 * VJF_BLK_LD] : 0.f;
+                        v[q].w = (!dg || c <= r4 + 3) ? p[3 * VJF_BLK_LD] : 0.f;
                     }
                 }
 #pragma unroll
@@ -562,7 +577,7 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                     const int idx = tid + q * VJF_CHOL_THREADS;
                     if (idx < ntri * 256) {
                         int b, c, r4; chol_tile_of(idx, b, c, r4);
-                        const int gi = s_bi[b] * 32 + r4, gj = s_bj[b] * 32 + c;          // X[gi..gi+3][gj]
+                        int gi, gj; tile_at(b, gi, gj); gi += r4; gj += c;                // X[gi..gi+3][gj]
                         if (gi < n && gj < n) *reinterpret_cast<float4*>(Wc + (size_t)gj * n + gi) = v[q];
                     }
                 }
@@ -578,7 +593,8 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
             //      odd-offset products of row nbl-1-w (<= ceil((nbl+1)/2) products each), partial tiles meet in LDS.
             {
                 float* s_pe = s_aux;                          // even partials, npad x DZP   (s_aux = Dinv is free now)
-                float* s_po = s_aux + (size_t)npad * DZP;     // odd partials
+                // odd partials: behind the even ones in s_aux; DZP = 32: s_aux holds one set only, the region reserved behind g
+                float* s_po = DZP <= 16 ? s_aux + (size_t)npad * DZP : s_g + (size_t)npad * DZP;
                 const int c = lane & 31, h = lane >> 5;
                 auto store_part = [&](const vjf_f32x16& acc, float* dst, int blk) {
                     if (c < DZP) {
@@ -598,14 +614,12 @@ __device__ __forceinline__ void vjf_chol_body(const VjfPlan& P, const VjfCholArg
                             // pass 1: row blocks    rb = row + par, row + par + 2, ... < nbl of X(rb, row)^T
                             for (int o = par; pass == 0 ? (row - o >= 0) : (row + o < nbl); o += 2) {
                                 const int ob = pass == 0 ? row - o : row + o;
-                                const float* xb = s_blk + (size_t)(pass == 0 ? vtri(row, ob) : vtri(ob, row)) * 1024;
+                                const float* xb = s_blk + (size_t)(pass == 0 ? vtri(row, ob) : vtri(ob, row)) * VJF_BLK_FLOATS;
                                 const float* sb = src + (size_t)ob * 32 * DZP;
                                 if (pass == 0)
-                                    blk_mma_f(acc, lane, [&](int i, int m) { return xb[vsw(i, m)]; },
-                                              [&](int m, int j) { return j < DZP ? sb[m * DZP + j] : 0.f; });
+                                    blk_mma_f<false>(acc, lane, xb, [&](int m, int j) { return j < DZP ? sb[m * DZP + j] : 0.f; });
                                 else
-                                    blk_mma_f(acc, lane, [&](int i, int m) { return xb[vsw(m, i)]; },
-                                              [&](int m, int j) { return j < DZP ? sb[m * DZP + j] : 0.f; });
+                                    blk_mma_f<true>(acc, lane, xb, [&](int m, int j) { return j < DZP ? sb[m * DZP + j] : 0.f; });
                             }
                             store_part(acc, par == 0 ? s_pe : s_po, row);
                         }

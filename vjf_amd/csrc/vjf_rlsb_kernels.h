@@ -44,7 +44,7 @@ template <bool WT> __device__ __forceinline__ float4 rlsc_ld4(const float* M, si
     return WT ? vjf_ld4_sc1(vjf_rsrc(M), (int)off) : *reinterpret_cast<const float4*>(M + off);
 }
 
-// 32x32 tile (bi, bj) of the n x n row-major matrix M -> XOR-swizzled LDS tile; outside the matrix: the identity
+// 32x32 tile (bi, bj) of the n x n row-major matrix M -> LDS block (vjf_chol_blocks.h); outside the matrix: the identity
 __device__ __forceinline__ void rlsb_tile_in(float* dst, const float* M, int n, int bi, int bj, int lane) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -129,7 +129,7 @@ __device__ __forceinline__ void rlsc_ld_rc(float (&v)[16], const float* M, int n
 #endif
 struct VjfRlscLds {
     float p[4][2][1024];
-    float d[1024], i[1024], t[1024];
+    float d[VJF_BLK_FLOATS], i[VJF_BLK_FLOATS], t[VJF_BLK_FLOATS];   // LDS blocks (33-float rows); p: accumulator images
     int good;
 };
 // step k of the sequence for workgroup `bid` (see above); every path ends in a return, no thread of the workgroup is left behind
@@ -137,14 +137,16 @@ struct VjfRlscLds {
 template <bool WT>
 __device__ __forceinline__ void rlsc_col_step(const VjfPlan& P, const VjfRlsbArgs& A, const int k, const int bid, VjfRlscLds& L) {
     float (&s_p)[4][2][1024] = L.p;
-    float (&s_d)[1024] = L.d;
-    float (&s_i)[1024] = L.i;
-    float (&s_t)[1024] = L.t;
+    float (&s_d)[VJF_BLK_FLOATS] = L.d;
+    float (&s_i)[VJF_BLK_FLOATS] = L.i;
+    float (&s_t)[VJF_BLK_FLOATS] = L.t;
     int& s_good = L.good;
     const int n = P.n, nbl = (n + 31) / 32, ncol = nbl - k, nahead = ncol > 1 ? ncol - 1 : 0;
     // (In the resident form the compiler hoists this function's lane-dependent address arithmetic out of the step loop and keeps
     //  it: 256 VGPRs + 208 B per lane of scratch instead of 160 VGPRs and none with the thread index made opaque per step -- and
-    //  is the FASTER of the two, 767-771 against 780-787 us per config E step on one box: the hoisted form stays.)
+    //  is the FASTER of the two, 767-771 against 780-787 us per config E step on one box: the hoisted form stays.
+    //  With 33-float block rows there are no per-lane XOR offsets left to hoist: 221 VGPRs and no scratch in this form, config E
+    //  as before, profiles/block_layout_isa.txt.)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool vec = (n & 3) == 0;
     float* Lm = A.Lw;
@@ -226,7 +228,7 @@ __device__ __forceinline__ void rlsc_col_step(const VjfPlan& P, const VjfRlsbArg
             vjf_f32x16 acc;
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-            blk_mma<true>(acc, s_t, s_i, 1.f, lane);               // T L_kk^-T
+            blk_mma<true>(acc, s_t, s_i, lane);               // T L_kk^-T
             rlsb_acc_out<WT>(acc, Lm, n, i, k, lane, false);
         }
         return;
@@ -294,7 +296,7 @@ __device__ __forceinline__ void rlsc_col_step(const VjfPlan& P, const VjfRlsbArg
         vjf_f32x16 acc;
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-        blk_mma<false>(acc, s_i, s_t, -1.f, lane);                 // -L_rr^-1 S
+        blk_mma<false, true>(acc, s_i, s_t, lane);                 // -L_rr^-1 S
         rlsb_acc_out<WT>(acc, A.X, n, r, j, lane, false);
     }
 }
