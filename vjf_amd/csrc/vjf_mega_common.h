@@ -240,15 +240,41 @@ __device__ __forceinline__ void mg_mma2_ld16(float (&a)[16], const float* __rest
 }
 // (mg_mmaN_mm16<2, VJF_MG_LD> written out ON PURPOSE: forwarding to the template grows vjf_mega_lite_kernel by 5612 bytes and its
 //  v_writelane / v_readlane count from 2936 to 3769 -- profiles/mega_split_isa.txt, candidate 4)
+template <bool SPLIT = true>
 __device__ __forceinline__ void mg_mma2_mm16(vjf_f32x4& acc0, vjf_f32x4& acc1, const float (&a)[16], const float* Xs, int M, int m0, int kb, int ke, int s0, int lane) {
     constexpr int LD = VJF_MG_LD;
     const int i = lane & 15, kk = lane >> 4;
     const bool rv = (m0 + i) < M;
     const float* xp = Xs + i;
     const int nst = (ke - kb + 3) >> 2, klast = ke - 1;
+    // full k-steps (4 (s + 1) <= ke - kb; kb is a multiple of 4): no clamp, the A operand masked by its row alone, B operands in chunks
+    // of four steps at immediate offsets 4 q LD and + 16 floats from one base (at most 60 LD + 16 floats = 7984 bytes), the next chunk's
+    // reads in front of this chunk's MFMAs (a chunk's steps behind the last full one read LDS rows that are not used: mg_mma2_lds).
+    // Then the one partial step, clamped and masked as before.  !SPLIT: every step that way (see mg_var2).
+    const int nf = SPLIT ? ((ke - kb) >> 2) - s0 : 0;   // full steps of this batch (uniform)
+    const float* xb = xp + (kb + 4 * s0 + kk) * LD;
+    float b[2][8];
+    auto rdb = [&](float (&bq)[8], int c4) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { bq[2 * c] = xb[4 * (c4 + c) * LD]; bq[2 * c + 1] = xb[4 * (c4 + c) * LD + 16]; }
+    };
+    if (nf > 0) rdb(b[0], 0);
+#pragma unroll
+    for (int c4 = 0; c4 < 16; c4 += 4) {
+        if (c4 < nf) {                                 // (uniform)
+            if (c4 + 4 < 16 && c4 + 4 < nf) rdb(b[((c4 >> 2) + 1) & 1], c4 + 4);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c4 + c < nf) {                     // (uniform)
+                    const float av = rv ? a[c4 + c] : 0.f;
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[(c4 >> 2) & 1][2 * c], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[(c4 >> 2) & 1][2 * c + 1], acc1, 0, 0, 0);
+                }
+        }
+    }
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        if (s0 + q < nst) {                            // (uniform)
+        if ((!SPLIT || q == nf) && s0 + q < nst) {     // (uniform) the partial step (!SPLIT: every step)
             const int k = kb + 4 * (s0 + q) + kk;
             const int kc = min(k, klast);
             const float av = (rv && k < ke) ? a[q] : 0.f;
@@ -324,16 +350,29 @@ __device__ __forceinline__ void mg_mma2(vjf_f32x4& acc0, vjf_f32x4& acc1, const 
 // drained between the tiles exposes an L2 round trip per tile).  Each tile's products run in ascending batch order, then its sum of
 // squares: the bits do not depend on how the batches are interleaved.
 // j0B < 0: no second tile; j0A < 0: none at all.
+// SPLIT (the Tanh training kernel): a tile's k range splits into full steps (16 (t + 1) <= K: with the triangle flag all of them, except in
+// the last row tile when n % 16 != 0) and at most one partial step (the dense walk's last one when n % 16 != 0).  A full step has no
+// clamp and no mask: its eight B operands are read at immediate offsets (16 q + c) LD and + 16 floats from ONE base per batch,
+// Xs + i + (4 kk + 16 t0) LD -- at most (48 + 3) LD + 16 floats = 6796 bytes, inside the 16 bits of the ds offset field; the base
+// advances with the batch, so the offsets do not grow with n (the route admits n <= 32 VJF_CHOL_MAXBLK = 224) -- and the next step's
+// reads are issued in front of this step's MFMAs.  rx must then be BOUNDED to the n x n floats of Xt (vjf_rsrc(base, n * n)): a lane
+// whose row j0 + i is >= n (the last row tile when n is no multiple of 16) loads zeros, what the select on (row valid) makes of its
+// operand.  The partial step keeps the clamped row of Xs and the masked A operand.  The k indices and the order of each accumulator's
+// MFMAs are those of the plain loop: the same bits (tools/var_mma_bench.hip, profiles/var_interior_bench.txt: V1).
+// !SPLIT (the other three kernels, see vjf_mega_trial.h: VSPLIT): every step is clamped and masked, rows >= n read row 0, rx may be
+// unbounded.
 // (mg_varN below is this routine for NG column groups, plain loads and batched B operands.  Two copies ON PURPOSE: with this one
 //  an instantiation of mg_varN, vjf_mega_kernel's scratch goes from 100 to 132 bytes -- profiles/mega_split_isa.txt, candidate 5)
+template <bool SPLIT = true>
 __device__ __forceinline__ void mg_var2(float& v2a, float& v2b, __amdgpu_buffer_rsrc_t rx, int n, int j0A, int KA, int j0B, int KB,
                                         const float* Xs, int lane) {
     constexpr int LD = VJF_MG_LD;
     if (j0A < 0) return;
     const int i = lane & 15, kk = lane >> 4;
     const bool rvA = (j0A + i) < n, rvB = j0B >= 0 && (j0B + i) < n;
-    const int offA = (rvA ? j0A + i : 0) * n + 4 * kk, offB = (rvB ? j0B + i : 0) * n + 4 * kk;
+    const int offA = (SPLIT || rvA ? j0A + i : 0) * n + 4 * kk, offB = (j0B >= 0 && (SPLIT || rvB) ? j0B + i : 0) * n + 4 * kk;   // (SPLIT, rows >= n: behind the descriptor's end)
     const float* xp = Xs + i;
+    const float* xq = xp + 4 * kk * LD;                                       // the full steps' base: + 16 t0 LD per batch
     const int ntA = (KA + 15) >> 4, ntB = j0B >= 0 ? (KB + 15) >> 4 : 0;
     const int SA = (ntA + 3) >> 2, SB = (ntB + 3) >> 2, S = SA + SB;
     vjf_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -355,9 +394,25 @@ __device__ __forceinline__ void mg_var2(float& v2a, float& v2b, __amdgpu_buffer_
             fold();
             acc0 = vjf_f32x4{0.f, 0.f, 0.f, 0.f}; acc1 = vjf_f32x4{0.f, 0.f, 0.f, 0.f};
         }
+        const int nf = SPLIT ? (ke >> 4) - t0 : 0;                            // full steps of this batch (uniform; <= 0: none, >= 4: all)
+        const float* xb = xq + 16 * t0 * LD;
+        float b[2][8];
+        auto rdb = [&](float (&bq)[8], int q) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { bq[2 * c] = xb[(16 * q + c) * LD]; bq[2 * c + 1] = xb[(16 * q + c) * LD + 16]; }
+        };
+        if (nf > 0) rdb(b[0], 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (t0 + q < nt) {                                                // (uniform)
+            if (q < nf) {                                                     // (uniform) a full step: no clamp, no mask
+                if (q + 1 < 4 && q + 1 < nf) rdb(b[(q + 1) & 1], q + 1);      // the next step's reads in front of this step's MFMAs
+                const float av[4] = {a[q].x, a[q].y, a[q].z, a[q].w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], b[q & 1][2 * c], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], b[q & 1][2 * c + 1], acc1, 0, 0, 0);
+                }
+            } else if (t0 + q < nt) {                                         // (uniform) the tile's one partial step
                 const int k0 = 16 * (t0 + q) + 4 * kk;
                 const float av[4] = {a[q].x, a[q].y, a[q].z, a[q].w};
 #pragma unroll
@@ -563,9 +618,10 @@ __device__ __forceinline__ void mg_sum_losses(const VjfMegaArgs& A, int t, float
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);                  \
     } while (0)
 
-// mg_var2 / mg_mma2_mm16 for NG column groups of 16 trials (NG = 2: one tile, LD = 33, the trial role's routines instruction for
-// instruction; NG = 4: two tiles side by side, LD = 65 -- every operand load of L^-1 and W then feeds twice the multiply-adds).  A
-// trial's sums run over k in the same order whatever NG is: the same bits.
+// mg_var2 / mg_mma2_mm16 for NG column groups of 16 trials (NG = 2: one tile, LD = 33; NG = 4: two tiles side by side, LD = 65 --
+// every operand load of L^-1 and W then feeds twice the multiply-adds).  A trial's sums run over k in the same order whatever NG
+// is: the same bits.  Every k-step is clamped and masked here: the split of mg_var2 into full and partial steps takes the moments
+// role's kernels from 92 / 100 to 224 bytes of scratch, with or without look-ahead (profiles/var_interior_isa.txt).
 template <int NG, int LD>
 __device__ __forceinline__ void mg_varN(float (&v2)[NG], __amdgpu_buffer_rsrc_t rx, int n, int j0A, int KA, int j0B, int KB, mg_lds_cf* Xs, int lane,
                                         const bool upper = true) {        // upper = false (uniform): column groups 2, 3 hold no trials, their multiply-adds are skipped

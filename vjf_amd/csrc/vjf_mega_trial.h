@@ -12,6 +12,10 @@
 template <bool RLS, bool ACT = false>
 __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaArgs& A, float* smem, const int wg, const VjfAct act = VjfAct{}) {
     constexpr int LD = VJF_MG_LD, NW = VJF_MG_WAVES, NT = VJF_MG_THREADS, TR = VJF_MG_TR;
+    // the variance and mean products with their k range split into full and partial steps (mg_var2): the Tanh training kernel only -- the
+    // kernels of the other activations have no registers for it, and vjf_mega_lite_kernel (whose moments role forms these products at
+    // the sizes that matter) ran 0.3 - 1.6 us a step slower in warm-up with it (profiles/var_interior_isa.txt, var_interior_ab.txt)
+    constexpr bool VSPLIT = RLS && !ACT;
     const int tid0 = threadIdx.x;
     const int dz = P.dz, dy = P.dy, du = P.du, n = P.n, din = P.din, dxu = P.dxu;
     const float* S = A.state;
@@ -270,7 +274,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             auto moments_a = [&]() {
             // ---- stage 2: predictive variance sum_j (Phi w_chol)_j^2 (module.py:75-76) and pt.mean = xs + Phi W (module.py:77)
             if (!replay) {
-                const __amdgpu_buffer_rsrc_t r_xt = vjf_rsrc(A.xt);
+                const __amdgpu_buffer_rsrc_t r_xt = VSPLIT ? vjf_rsrc(A.xt, (size_t)n * n) : vjf_rsrc(A.xt);   // (bounded: rows >= n of the last row tile load zeros, see mg_var2)
                 const float* Wm = S + P.off[VJF_SLOT_W_MEAN];
                 const int ntile = (n + 15) >> 4;
                 float v2a = 0.f, v2b = 0.f;
@@ -295,7 +299,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                         Kp[h] = tri ? min(n, tt * 16 + 16) : n;
                     }
                     if (j0p[0] < 0) { j0p[0] = j0p[1]; Kp[0] = Kp[1]; j0p[1] = -1; }
-                    mg_var2(v2a, v2b, r_xt, n, j0p[0], Kp[0], j0p[1], Kp[1], s_phi, lane);
+                    mg_var2<VSPLIT>(v2a, v2b, r_xt, n, j0p[0], Kp[0], j0p[1], Kp[1], s_phi, lane);
                 }
                 if (first) VJF_MG_STAMP(22);
                 v2a += __shfl_xor(v2a, 16, 64); v2a += __shfl_xor(v2a, 32, 64);
@@ -304,7 +308,7 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 if (wave < nsl) {
                     const int sl = msl;
                     vjf_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-                    if (mpre) { if (mke > mkb) mg_mma2_mm16(acc0, acc1, am, s_phi, dz, 0, mkb, mke, 0, lane); }
+                    if (mpre) { if (mke > mkb) mg_mma2_mm16<VSPLIT>(acc0, acc1, am, s_phi, dz, 0, mkb, mke, 0, lane); }
                     else mg_mma2(acc0, acc1, Wm, dz, dz, 0, s_phi, mkb, mke, lane);
                     float* pr = s_part + (size_t)(sl * 16 + 4 * (lane >> 4)) * LD + (lane & 15);
 #pragma unroll
