@@ -2,11 +2,13 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--plot out.png]
 
 With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
 the +-2 sd band of the first latent at a few steps.  With --lyapunov N it prints the Lyapunov spectrum of the learned flow over N steps
-from the last posterior mean (`lyapunov`) and the moduli of the Jacobian's eigenvalues there (`jacobian`).
+from the last posterior mean (`lyapunov`) and the moduli of the Jacobian's eigenvalues there (`jacobian`).  With --fixed-points N it
+searches for the fixed points of the learned flow from N of the filtered posterior means (`fixed_points`) and prints each distinct one,
+its residual, the moduli of the eigenvalues of the Jacobian there and whether it is stable.
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -30,6 +32,7 @@ def main(argv=None):
     ap.add_argument("--forecast", type=int, default=200)
     ap.add_argument("--ensemble", type=int, default=0, help="members of the forecast with uncertainty (0: skip it), e.g. 64")
     ap.add_argument("--lyapunov", type=int, default=0, help="steps of the Lyapunov spectrum of the learned flow (0: skip it), e.g. 10000")
+    ap.add_argument("--fixed-points", type=int, default=0, help="starts of the search for fixed points of the learned flow (0: skip it), e.g. 64")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -64,6 +67,19 @@ def main(argv=None):
               f"  sum = {float(ly.exponents[0].sum()):+.5f}")
         ev = torch.linalg.eigvals(model.jacobian(q_last)[0].cpu())
         print("jacobian at the last posterior mean: |eigenvalues| =", [round(float(v), 4) for v in ev.abs()])
+    if a.fixed_points > 0:
+        # where the learned flow stands still, and whether it stays there: N starts drawn from the filtered posterior means, the whole
+        # damped Newton search of every start in one native call; a fixed point is stable if every eigenvalue of the Jacobian of the
+        # map lies inside the unit circle
+        rows = torch.randint(0, m.shape[0], (a.fixed_points,), generator=torch.Generator().manual_seed(2))
+        fp = model.fixed_points(m[rows])
+        ux, uj, count = fp.unique()
+        print(f"fixed points: {int(fp.converged.sum())} of {a.fixed_points} starts converged, {len(ux)} distinct")
+        for xk, jk, ck in zip(ux.cpu(), uj.cpu(), count):
+            near = ((fp.x.cpu() - xk).norm(dim=1) <= 1e-3) & fp.converged.cpu()
+            mod = torch.linalg.eigvals(jk).abs()
+            print(f"  x = {[round(float(v), 4) for v in xk]}  residual = {float(fp.residual.cpu()[near].max()):.2e}  reached by {int(ck)}"
+                  f"  |eigenvalues| = {[round(float(v), 4) for v in mod]}  {'stable' if bool((mod < 1).all()) else 'unstable'}")
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

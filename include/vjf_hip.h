@@ -314,6 +314,29 @@ int vjf_tangent_plan(int32_t n, int32_t d, int32_t dout, int32_t m, int32_t* vec
 int vjf_tangent_rollout(const float* x0, const float* u, const float* q0, const float* centroid, const float* logwidth,
                         const float* w_mean, float* x_out, float* q_out, float* lsum, float* lhist, int32_t T, int32_t B,
                         int32_t n, int32_t d, int32_t dout, int32_t m, int32_t qr_every, int32_t accumulate, void* stream);
+/* Fixed points of the same mean map: for each start x0[b] and constant input u[b] (a parameter of the map), x with
+ *   g(x, u) = Phi([x, u]) w_mean = 0,   A = dg/dx = -w_mean^T G  (J = I + A),
+ * by a damped Newton (Levenberg-Marquardt) search on |g|^2, the whole search as one call, fp32.  Per trial: x = xc = x0, r2 = +inf,
+ * lam = lam0, M = 0 (dout x dout), b = 0 (dout), done = false, n_iter = 0.  For k = 0 .. max_iter, for every trial not done:
+ *   1. g = g(xc, u), A = A(xc, u), r2c = sum_i g_i^2;
+ *   2. r2c < r2 (a NaN compares false): accept -- x = xc, r2 = r2c, M = A^T A, b = A^T g, and with k > 0 lam = max(lam / 10, 1e-7);
+ *   3. else reject -- lam = min(lam * 10, 1e7);
+ *   4. done = (r2 <= tol^2);   5. k == max_iter: stop;
+ *   6. not done: n_iter += 1, mu = trace(M) / dout, K = M + (lam mu) I = L L^T (Cholesky), K delta = -b, xc = x + delta; a pivot that
+ *      is not positive and finite: xc = x (the next comparison rejects it).
+ * A trial that is done is frozen.  So r2 never increases, max_iter = 0 returns x0 and its residual, a non-finite start returns x0,
+ * residual = inf, converged = 0, and a trial's outputs depend on that trial's inputs alone, bit for bit (not on its row, the batch, the
+ * other trials of its tile or the stream).
+ * x0 (B,dout); u (B,du) or NULL (du = d - dout); x (B,dout); residual (B) = sqrt(r2); n_iter (B), converged (B): int32; jac (B,dout,dout)
+ * or NULL: J = I + A at the returned x, jac[b][i][j] = df_i/dx_j.  Asynchronous on `stream`, no host synchronisation, no scratch; reads
+ * the state tensors, writes none.
+ * -1 null tensor, -20 bad shape (also max_iter < 0, tol or lam0 not positive and finite), -21 u missing with d > dout, -11 dout > 32 or
+ * the shape is beyond one workgroup's LDS: all before the first launch.
+ * vjf_fixed_points_plan: the dynamic LDS of a workgroup for these sizes; -11 / -20 as the call. */
+int vjf_fixed_points_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes);
+int vjf_fixed_points(const float* x0, const float* u, const float* centroid, const float* logwidth, const float* w_mean,
+                     float* x, float* residual, int32_t* n_iter, int32_t* converged, float* jac,
+                     int32_t B, int32_t n, int32_t d, int32_t dout, int32_t max_iter, float tol, float lam0, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

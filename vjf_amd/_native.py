@@ -86,6 +86,8 @@ SIGNATURES = {
     "vjf_forecast_ens": [_P, C.c_int64] + [_P] * 16 + [_I] * 7 + [_P],
     "vjf_tangent_plan": [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(C.c_int64)],
     "vjf_tangent_rollout": [_P] * 10 + [_I] * 8 + [_P],
+    "vjf_fixed_points_plan": [_I, _I, _I, C.POINTER(C.c_int64)],
+    "vjf_fixed_points": [_P] * 10 + [_I] * 5 + [_F, _F, _P],
     "vjf_rls_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_blr_rls": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_kalman_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],

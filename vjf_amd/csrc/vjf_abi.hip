@@ -38,6 +38,7 @@
 #include "vjf_host_ops.h"
 #include "vjf_host_forecast.h"
 #include "vjf_host_tangent.h"
+#include "vjf_host_fixed_point.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -515,6 +516,34 @@ int vjf_tangent_rollout(const float* x0, const float* u, const float* q0, const 
     a.u = u; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.x_out = x_out; a.q_out = q_out; a.lsum = lsum; a.lhist = lhist;
     a.B = B; a.n = n; a.d = d; a.dout = dout; a.m = m; a.qr = qr_every;
     return tangent_run(a, x0, q0, T, accumulate != 0, p, fc_env_int("VJF_FC_CHUNK"), (hipStream_t)stream);
+}
+
+int vjf_fixed_points_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout) return fail(-20, "vjf_fixed_points_plan: bad shape (n=%d d=%d dout=%d)", n, d, dout);
+    const FpPlan p = fp_plan(n, d, dout, fc_env_on("VJF_FC_CENTROID_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_fixed_points_plan: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_FP_MAXDOUT ? "dout <= 32 (VJF_FP_MAXDOUT)" : "one workgroup's LDS");
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_fixed_points(const float* x0, const float* u, const float* centroid, const float* logwidth, const float* w_mean, float* x,
+                     float* residual, int32_t* n_iter, int32_t* converged, float* jac, int32_t B, int32_t n, int32_t d, int32_t dout,
+                     int32_t max_iter, float tol, float lam0, void* stream) {
+    if (!x0 || !centroid || !logwidth || !w_mean || !x || !residual || !n_iter || !converged) return fail(-1, "vjf_fixed_points: null tensor");
+    if (B < 1 || n < 1 || dout < 1 || d < dout || max_iter < 0 || !(tol > 0.f && tol < INFINITY) || !(lam0 > 0.f && lam0 < INFINITY))
+        return fail(-20, "vjf_fixed_points: bad shape (B=%d n=%d d=%d dout=%d max_iter=%d tol=%g lam0=%g)", B, n, d, dout, max_iter, (double)tol,
+                    (double)lam0);
+    if (d > dout && !u) return fail(-21, "vjf_fixed_points: u is required when d > dout");
+    const FpPlan p = fp_plan(n, d, dout, fc_env_on("VJF_FC_CENTROID_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_fixed_points: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_FP_MAXDOUT ? "dout <= 32 (VJF_FP_MAXDOUT)" : "one workgroup's LDS");
+    VjfFpArgs a{};
+    a.x0 = x0; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.x = x; a.residual = residual; a.n_iter = n_iter;
+    a.converged = converged; a.jac = jac; a.B = B; a.n = n; a.d = d; a.dout = dout; a.max_iter = max_iter; a.tol = tol; a.lam0 = lam0;
+    return fixed_point_run(a, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

@@ -74,6 +74,32 @@ ForecastEnsemble = namedtuple('ForecastEnsemble', ['x_mean', 'x_var', 'y_mean', 
 # what RBFDS.lyapunov / VJF.lyapunov return: the exponents (B, m) in Gram-Schmidt column order, the final state (B, xdim) and
 # orthonormal frame (B, xdim, m), and the per-interval log R_vv (ceil(n_step / qr_every), B, m) or None
 LyapunovResult = namedtuple('LyapunovResult', ['exponents', 'x', 'q', 'log_stretch'])
+FP_MAX_XDIM = 32                         # VJF_FP_MAXDOUT of vjf_fixed_points
+
+
+class FixedPointResult(namedtuple('FixedPointResult', ['x', 'residual', 'converged', 'n_iter', 'jacobian'])):
+    """What RBFDS.fixed_points / VJF.fixed_points return, per start: where the search ended x (B, xdim), |g(x)| there residual (B,),
+    whether that is within `tol` converged (B,) bool, the steps taken n_iter (B,) int32 and the Jacobian of the mean map at x,
+    jacobian (B, xdim, xdim), or None."""
+    __slots__ = ()
+
+    def unique(self, merge_tol: float = 1e-3):
+        """The distinct fixed points among the converged rows, on the host: a row is kept if it is farther (Euclidean) than
+        `merge_tol` from every row kept before it, in row order.
+        :return: (x (K, xdim), jacobian (K, xdim, xdim) or None, count (K,) int64: the starts that reached each)"""
+        idx = torch.nonzero(self.converged.cpu()).flatten()
+        x = self.x.detach().cpu()
+        kept, count = [], []
+        for i in idx.tolist():
+            for q, r in enumerate(kept):
+                if float((x[i] - x[r]).norm()) <= merge_tol:
+                    count[q] += 1
+                    break
+            else:
+                kept.append(i)
+                count.append(1)
+        rows = torch.as_tensor(kept, dtype=torch.long, device=self.x.device)
+        return self.x[rows], None if self.jacobian is None else self.jacobian[rows], torch.as_tensor(count, dtype=torch.long)
 
 
 class LinearDecoder(Module):
@@ -455,6 +481,43 @@ class RBFDS(Module):
         x, q, lsum, hist = self._tangent(x0, None if u is None else u[T0:], q0, T, m, qr, history=return_history)
         exponents = lsum / (T * dt) if T > 0 else torch.full_like(lsum, float('nan'))
         return LyapunovResult(exponents, x, q, hist)
+
+    def fixed_points(self, x0: Tensor, u: Tensor = None, *, max_iter: int = 64, tol: float = 1e-5, damping: float = 1e-3,
+                     return_jacobian: bool = True) -> FixedPointResult:
+        """Fixed points of the mean map, x with g(x, u) = Phi([x, u]) w_mean = 0, from every start of `x0` as ONE C-ABI call
+        (vjf_fixed_points): a damped Newton (Levenberg-Marquardt) search on |g|^2 whose whole iteration stays on chip -- a step is
+        accepted only if it lowers |g|, the damping falls by 10 after an accepted step and rises by 10 after a rejected one.
+        :param x0: (B, xdim), the starts;  :param u: (B, udim), a constant input per start: a parameter of the map
+        :param max_iter: candidates tried at most;  :param tol: a start has converged once |g(x)| <= tol
+        :param damping: the first damping, relative to the mean diagonal of A^T A (A = dg/dx)
+        :return: FixedPointResult(x (B, xdim), residual (B,), converged (B,) bool, n_iter (B,) int32, jacobian (B, xdim, xdim) =
+            d f / d x of f = x + g at x if `return_jacobian` else None).  A start that has not converged returns the best point it
+            reached (never worse than the start); the moduli of the eigenvalues of `jacobian` tell a stable fixed point (all < 1).
+        Asynchronous; reads the model's state and writes none; no scratch."""
+        x0 = dev32(x0)
+        B, dout = x0.shape
+        assert dout == self.velocity.n_output, f"x0 has {dout} columns, expected xdim={self.velocity.n_output}"
+        if dout > FP_MAX_XDIM:
+            raise NotImplementedError(f"fixed_points covers xdim <= {FP_MAX_XDIM}, this model has xdim = {dout}")
+        max_iter, tol, damping = int(max_iter), float(tol), float(damping)
+        if max_iter < 0:
+            raise ValueError(f"max_iter must not be negative, got {max_iter}")
+        if not 0. < tol < float('inf'):
+            raise ValueError(f"tol must be positive and finite, got {tol}")
+        if not 0. < damping < float('inf'):
+            raise ValueError(f"damping must be positive and finite, got {damping}")
+        if u is not None:
+            u = dev32(u)[None]
+        u = self._tangent_u(u, 1, B)
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, device=x0.device, dtype=dtype)      # noqa: E731
+        x, residual, n_iter, conv = new(B, dout), new(B), new(B, dtype=torch.int32), new(B, dtype=torch.int32)
+        jac = new(B, dout, dout) if return_jacobian else None
+        N.check(N.lib().vjf_fixed_points(N.ptr(x0), N.ptr(u), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth), N.ptr(vel.w_mean),
+                                         N.ptr(x), N.ptr(residual), N.ptr(n_iter), N.ptr(conv), N.ptr(jac), B, n, d, dout, max_iter,
+                                         tol, damping, stream_ptr()), "vjf_fixed_points")
+        return FixedPointResult(x, residual, conv != 0, n_iter, jac)
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1130,3 +1193,10 @@ class VJF(Module):
         the columns mean); a Gaussian stands for its mean, e.g. the last posterior `filter` returned."""
         return self.transition.lyapunov(x0.mean if isinstance(x0, Gaussian) else x0, u, n_step, n_exponent=n_exponent,
                                         qr_every=qr_every, q0=q0, burn_in=burn_in, dt=dt, return_history=return_history)
+
+    def fixed_points(self, x0: Union[Tensor, Gaussian], u: Tensor = None, *, max_iter: int = 64, tol: float = 1e-5,
+                     damping: float = 1e-3, return_jacobian: bool = True) -> FixedPointResult:
+        """The fixed points of the learned mean map reached from the starts `x0` in one native call (RBFDS.fixed_points has the
+        arguments); a Gaussian stands for its mean, e.g. the last posterior `filter` returned."""
+        return self.transition.fixed_points(x0.mean if isinstance(x0, Gaussian) else x0, u, max_iter=max_iter, tol=tol,
+                                            damping=damping, return_jacobian=return_jacobian)
