@@ -337,6 +337,38 @@ int vjf_fixed_points_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes
 int vjf_fixed_points(const float* x0, const float* u, const float* centroid, const float* logwidth, const float* w_mean,
                      float* x, float* residual, int32_t* n_iter, int32_t* converged, float* jac,
                      int32_t B, int32_t n, int32_t d, int32_t dout, int32_t max_iter, float tol, float lam0, void* stream);
+/* Smoothing: the extended Rauch-Tung-Striebel pass over a filtered sequence q(x_t | y_1..t) = N(mu_t, D_t), D_t = diag(exp(logvar_t)),
+ * with the same mean map f(x, u) = x + Phi([x, u]) w_mean, J = I + A its Jacobian, and a scalar state-noise variance q = state_var,
+ * the whole horizon as one call, fp32.  The transition from row t to row t + 1 uses u[t + 1] (u[0] is never read: the array that went
+ * into the filter goes in unchanged).  Per trial:
+ *   last row:  ms_{T-1} = mu_{T-1} (bit for bit),  Ps_{T-1} = D_{T-1};
+ *   for t = T-2 .. 0, with g = g(mu_t, u_{t+1}), J = J(mu_t, u_{t+1}), sd = exp(logvar_t / 2):
+ *     1. Jh = J diag(sd) / sqrt(q);
+ *     2. M = I + Jh^T Jh = L L^T (Cholesky; eigenvalues >= 1 whatever logvar is);
+ *     3. G = diag(sd) M^-1 Jh^T / sqrt(q)      (= D J^T (J D J^T + q I)^-1, the smoother gain);
+ *     4. C = diag(sd) M^-1 diag(sd)            (= D - D J^T (J D J^T + q I)^-1 J D);
+ *     5. ms_t = mu_t + G (ms_{t+1} - (mu_t + g));
+ *     6. Ps_{t+1} = Ls Ls^T (Cholesky), K = G Ls, Ps_t = C + K K^T.
+ * This is the information form of the textbook Ps_t = D + G (Ps_{t+1} - P^-) G^T: no difference of positive-definite matrices.
+ * Carried between rows: ms and the lower triangle of Ps, in fp32.  With after_mean (B,dout) and after_cov (B,dout,dout; its lower
+ * triangle is read) -- the smoothed moments of the row behind the last one -- row T-1 is smoothed like every other row, u has T + 1
+ * rows and u[T] drives the step into the after-row: rows [k, T) first and rows [0, k) second with after = (mean[k], cov[k]) give the
+ * bits of the undivided call.
+ * mu, logvar (T,B,dout); u (T,B,du), with after_* (T+1,B,du), or NULL (du = d - dout); mean, var (T,B,dout): ms and the diagonal of Ps;
+ * cov (T,B,dout,dout) or NULL: Ps written from its triangle -- exactly symmetric, its diagonal is var bit for bit; cov0 (B,dout,dout):
+ * Ps_0, always written.  A trial with an input that is not finite at row t (mu, logvar, u, after_*), or with a pivot of a factor
+ * that is not positive and finite (possible only through after_cov), has NaN in every output from that row back to row 0; its
+ * outputs behind that row and every other trial keep their bits.  No loop bound depends on data.  A trial's outputs depend on that
+ * trial's inputs alone, bit for bit (not on its row, the batch, the other trials of its tile or the stream).  Asynchronous on
+ * `stream`, no host synchronisation, no scratch; reads the state tensors, writes none.
+ * -1 null tensor, -20 bad shape (also T < 1, state_var not positive and finite, one of after_mean / after_cov without the other), -21 u
+ * missing with d > dout (and a transition to take), -11 dout > 32 or the shape is beyond one workgroup's LDS (every dout <= 24 with
+ * n <= 256 and du <= 8 fits): all before the first launch.
+ * vjf_smooth_plan: the dynamic LDS of a workgroup for these sizes; -11 / -20 as the call. */
+int vjf_smooth_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes);
+int vjf_smooth(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth,
+               const float* w_mean, const float* after_mean, const float* after_cov, float* mean, float* var, float* cov,
+               float* cov0, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, float state_var, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

@@ -39,6 +39,7 @@
 #include "vjf_host_forecast.h"
 #include "vjf_host_tangent.h"
 #include "vjf_host_fixed_point.h"
+#include "vjf_host_smooth.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -544,6 +545,35 @@ int vjf_fixed_points(const float* x0, const float* u, const float* centroid, con
     a.x0 = x0; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.x = x; a.residual = residual; a.n_iter = n_iter;
     a.converged = converged; a.jac = jac; a.B = B; a.n = n; a.d = d; a.dout = dout; a.max_iter = max_iter; a.tol = tol; a.lam0 = lam0;
     return fixed_point_run(a, p, (hipStream_t)stream);
+}
+
+int vjf_smooth_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout) return fail(-20, "vjf_smooth_plan: bad shape (n=%d d=%d dout=%d)", n, d, dout);
+    const SmPlan p = sm_plan(n, d, dout, fc_env_on("VJF_FC_CENTROID_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_smooth_plan: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_SM_MAXDOUT ? "dout <= 32 (VJF_SM_MAXDOUT)" : "one workgroup's LDS");
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_smooth(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth, const float* w_mean,
+               const float* after_mean, const float* after_cov, float* mean, float* var, float* cov, float* cov0, int32_t T, int32_t B,
+               int32_t n, int32_t d, int32_t dout, float state_var, void* stream) {
+    if (!mu || !logvar || !centroid || !logwidth || !w_mean || !mean || !var || !cov0) return fail(-1, "vjf_smooth: null tensor");
+    if (T < 1 || B < 1 || n < 1 || dout < 1 || d < dout || !(state_var > 0.f && state_var < INFINITY) || !after_mean != !after_cov)
+        return fail(-20, "vjf_smooth: bad shape (T=%d B=%d n=%d d=%d dout=%d state_var=%g%s)", T, B, n, d, dout, (double)state_var,
+                    !after_mean != !after_cov ? ", one of after_mean / after_cov without the other" : "");
+    if (d > dout && !u && (T > 1 || after_mean)) return fail(-21, "vjf_smooth: u is required when d > dout");
+    const SmPlan p = sm_plan(n, d, dout, fc_env_on("VJF_FC_CENTROID_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_smooth: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_SM_MAXDOUT ? "dout <= 32 (VJF_SM_MAXDOUT)" : "one workgroup's LDS");
+    VjfSmArgs a{};
+    a.mu = mu; a.lv = logvar; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.after_mean = after_mean;
+    a.after_cov = after_cov; a.mean = mean; a.var = var; a.cov = cov; a.cov0 = cov0; a.T = T; a.B = B; a.n = n; a.d = d; a.dout = dout;
+    a.rsq = 1.f / sqrtf(state_var);
+    return smooth_run(a, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

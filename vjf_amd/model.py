@@ -75,6 +75,7 @@ ForecastEnsemble = namedtuple('ForecastEnsemble', ['x_mean', 'x_var', 'y_mean', 
 # orthonormal frame (B, xdim, m), and the per-interval log R_vv (ceil(n_step / qr_every), B, m) or None
 LyapunovResult = namedtuple('LyapunovResult', ['exponents', 'x', 'q', 'log_stretch'])
 FP_MAX_XDIM = 32                         # VJF_FP_MAXDOUT of vjf_fixed_points
+SM_MAX_XDIM = 32                         # VJF_SM_MAXDOUT of vjf_smooth
 
 
 class FixedPointResult(namedtuple('FixedPointResult', ['x', 'residual', 'converged', 'n_iter', 'jacobian'])):
@@ -100,6 +101,17 @@ class FixedPointResult(namedtuple('FixedPointResult', ['x', 'residual', 'converg
                 count.append(1)
         rows = torch.as_tensor(kept, dtype=torch.long, device=self.x.device)
         return self.x[rows], None if self.jacobian is None else self.jacobian[rows], torch.as_tensor(count, dtype=torch.long)
+
+
+class SmoothResult(namedtuple('SmoothResult', ['mean', 'var', 'cov', 'head'])):
+    """What RBFDS.smooth / VJF.smooth return: the smoothed means (T, B, xdim), the marginal variances var (T, B, xdim), the full
+    covariances cov (T, B, xdim, xdim) or None, and head = (mean[0], cov of row 0 (B, xdim, xdim)): what a call on the rows before these
+    takes as `after`."""
+    __slots__ = ()
+
+    def gaussian(self) -> Gaussian:
+        """The smoothed marginals as the filter returns its posterior: Gaussian(mean, log var), e.g. for `model.decoder`."""
+        return Gaussian(self.mean, self.var.log())
 
 
 class LinearDecoder(Module):
@@ -518,6 +530,64 @@ class RBFDS(Module):
                                          N.ptr(x), N.ptr(residual), N.ptr(n_iter), N.ptr(conv), N.ptr(jac), B, n, d, dout, max_iter,
                                          tol, damping, stream_ptr()), "vjf_fixed_points")
         return FixedPointResult(x, residual, conv != 0, n_iter, jac)
+
+    def smooth(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, *, state_var: float = None,
+               after: Tuple[Tensor, Tensor] = None, return_cov: bool = False) -> SmoothResult:
+        """The smoothed posterior q(x_t | y_1..T) of a filtered sequence as ONE C-ABI call (vjf_smooth): the extended
+        Rauch-Tung-Striebel pass with the learned mean map and its Jacobian, backwards over the whole record on chip, in the
+        information form stated in include/vjf_hip.h (a sum of two positive semi-definite terms per row, one factorisation of a matrix
+        bounded below by I).
+        :param q: the filtered posterior, a Gaussian or a (mu, logvar) pair of (T, B, xdim) -- what `filter_sequence` / `fit` return;
+            a (T, xdim) pair is one trial
+        :param u: (T, B, udim), the array that went into the filter (the step from row t to t + 1 reads u[t + 1]; u[0] is never
+            read); with `after`, (T + 1, B, udim): u[T] drives the step into the after-row
+        :param state_var: the scalar state-noise variance, positive; default exp(self.logvar) -- reading that default copies one
+            scalar to the host, which synchronises the stream; pass a float to stay asynchronous
+        :param after: (mean (B, xdim), cov (B, xdim, xdim)), the smoothed moments of the row behind the last one, such as a previous
+            result's `head`: smoothing rows [k, T) first and rows [0, k) with after = that head second gives the bits of one call
+        :param return_cov: also return the full covariances
+        :return: SmoothResult(mean, var (T, B, xdim), cov (T, B, xdim, xdim) or None, head = (mean[0], cov of row 0)).  A trial with
+            a non-finite input at some row has NaN from that row back to row 0.
+        Reads the model's state and writes none; no scratch."""
+        mu, lv = (q.mean, q.logvar) if isinstance(q, Gaussian) else q
+        mu, lv = dev32(mu, ndim2=False), dev32(lv, ndim2=False)
+        mu, lv = (t[:, None, :] if t.ndim == 2 else t for t in (mu, lv))        # (T, xdim): one trial
+        assert mu.ndim == 3 and lv.shape == mu.shape, f"q is {tuple(mu.shape)} and {tuple(lv.shape)}, expected two (T, B, xdim)"
+        mu, lv = mu.contiguous(), lv.contiguous()
+        T, B, dout = mu.shape
+        assert T >= 1, 'q must have at least one row'
+        assert dout == self.velocity.n_output, f"q has {dout} columns, expected xdim={self.velocity.n_output}"
+        if dout > SM_MAX_XDIM:
+            raise NotImplementedError(f"smooth covers xdim <= {SM_MAX_XDIM}, this model has xdim = {dout}")
+        state_var = float(self.logvar.exp()) if state_var is None else float(state_var)
+        if not 0. < state_var < float('inf'):
+            raise ValueError(f"state_var must be positive and finite, got {state_var}")
+        a_mean = a_cov = None
+        if after is not None:
+            a_mean, a_cov = after
+            a_mean, a_cov = dev32(a_mean), dev32(a_cov, ndim2=False)
+            if a_cov.ndim == 2:
+                a_cov = a_cov[None]
+            assert a_mean.shape == (B, dout), f"after[0] is {tuple(a_mean.shape)}, expected {(B, dout)}"
+            assert a_cov.shape == (B, dout, dout), f"after[1] is {tuple(a_cov.shape)}, expected {(B, dout, dout)}"
+            a_cov = a_cov.contiguous()
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        rows = T + (after is not None)
+        if d > dout and u is not None:
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == rows, f"u has {u.shape[0]} rows, expected {rows} (T{' + 1 with `after`' if after is not None else ''})"
+        u = self._tangent_u(u, rows, B)
+        new = lambda *shape: torch.empty(*shape, device=mu.device, dtype=torch.float32)      # noqa: E731
+        mean, var, cov0 = new(T, B, dout), new(T, B, dout), new(B, dout, dout)
+        cov = new(T, B, dout, dout) if return_cov else None
+        rc = N.lib().vjf_smooth(N.ptr(mu), N.ptr(lv), N.ptr(u), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                                N.ptr(vel.w_mean), N.ptr(a_mean), N.ptr(a_cov), N.ptr(mean), N.ptr(var), N.ptr(cov), N.ptr(cov0),
+                                T, B, n, d, dout, state_var, stream_ptr())
+        if rc == -11:                             # the shape is beyond the plan (vjf_smooth_plan): nothing was launched
+            raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_smooth")
+        return SmoothResult(mean, var, cov, (mean[0], cov0))
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1200,3 +1270,9 @@ class VJF(Module):
         arguments); a Gaussian stands for its mean, e.g. the last posterior `filter` returned."""
         return self.transition.fixed_points(x0.mean if isinstance(x0, Gaussian) else x0, u, max_iter=max_iter, tol=tol,
                                             damping=damping, return_jacobian=return_jacobian)
+
+    def smooth(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, *, state_var: float = None,
+               after: Tuple[Tensor, Tensor] = None, return_cov: bool = False) -> SmoothResult:
+        """The smoothed posterior q(x_t | y_1..T) of a filtered sequence -- what `filter_sequence` / `fit` returned -- in one native
+        call (RBFDS.smooth has the arguments); `model.decoder(res.gaussian().mean)` gives the smoothed observations."""
+        return self.transition.smooth(q, u, state_var=state_var, after=after, return_cov=return_cov)
