@@ -369,6 +369,38 @@ int vjf_smooth_plan(int32_t n, int32_t d, int32_t dout, int64_t* lds_bytes);
 int vjf_smooth(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth,
                const float* w_mean, const float* after_mean, const float* after_cov, float* mean, float* var, float* cov,
                float* cov0, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, float state_var, void* stream);
+/* Posterior draws: S joint draws per trial from the smoothed posterior of a filtered sequence by backward sampling, the whole horizon as
+ * one call, fp32.  Notation and inputs of vjf_smooth: f = x + g, J = I + A at (mu_t, u_{t+1}), sd = exp(logvar_t / 2), q = state_var; the
+ * step from row t to row t + 1 uses u[t + 1].  noise z is standard normal, (S,T,B,dout).  Per trial and member s:
+ *   last row:  x_{T-1} = mu_{T-1} + sd_{T-1} z_{T-1}   (one fused multiply-add);
+ *   for t = T-2 .. 0, with g = g(mu_t, u_{t+1}), J = J(mu_t, u_{t+1}), sd = exp(logvar_t / 2):
+ *     1. Jh = J diag(sd) / sqrt(q);
+ *     2. M = I + Jh^T Jh = L L^T (Cholesky);
+ *     3. G = diag(sd) M^-1 Jh^T / sqrt(q)                     (steps 1 to 3 are vjf_smooth's, the same arithmetic, once per trial);
+ *     4. L^T w = z_t                                          (one back-substitution per member);
+ *     5. x_t = (mu_t + G (x_{t+1} - (mu_t + g))) + sd w       (the mean sum in vjf_smooth's order, the noise term added last by one
+ *                                                              fused multiply-add: with z = 0 the draw is vjf_smooth's mean, bit for bit).
+ * sd L^-T z has covariance diag(sd) M^-1 diag(sd), the C of vjf_smooth, and x_t is affine in x_{t+1} (the linearisation point is mu_t, not
+ * the draw), so the draws are exactly Gaussian: their row means are vjf_smooth's ms_t, their row covariances Ps_t and
+ * Cov(x_t, x_{t+1}) = G_t Ps_{t+1}.  Carried between rows: x alone.  With after (S,B,dout) -- the draws of the row behind the last one --
+ * row T-1 is drawn like every other row from z[:, T-1], u has T + 1 rows and u[T] drives the step into the after-row: rows [k, T) first
+ * and rows [0, k) second with after = x[:, k] give the bits of the undivided call.
+ * mu, logvar (T,B,dout); u (T,B,du), with after (T+1,B,du), or NULL (du = d - dout); noise, x (S,T,B,dout).  A trial with an input that
+ * is not finite at row t (mu, logvar, u) has NaN in every member from that row back to row 0.  A member whose noise is NaN at row t,
+ * component c, has NaN by propagation: components 0 .. c of row t (those the back-substitution reaches) and every component from row
+ * t - 1 back; a non-finite after-row of a member likewise from row T-1 back.  The rows behind, the other members and every other trial
+ * keep their bits.  No loop bound depends on data.  A member's draws depend on that trial's inputs and that member's noise alone, bit
+ * for bit (not on S, its index, the members per workgroup, the trial's row, the batch, its tile-mates or the stream).  Asynchronous on
+ * `stream`, no host synchronisation, no scratch; reads the state tensors, writes none.
+ * -1 null tensor, -20 bad shape (also T < 1, S < 1, state_var not positive and finite), -21 u missing with d > dout (and a transition to
+ * take), -11 dout > 32 or the shape is beyond one workgroup's LDS (every shape vjf_smooth accepts is accepted): all before the first
+ * launch.
+ * vjf_smooth_sample_plan: the members a workgroup carries (<= S; the launch has ceil(B / 16) x ceil(S / members) workgroups) and its
+ * dynamic LDS for these sizes; either pointer may be NULL; -11 / -20 as the call. */
+int vjf_smooth_sample_plan(int32_t n, int32_t d, int32_t dout, int32_t S, int32_t* members_per_workgroup, int64_t* lds_bytes);
+int vjf_smooth_sample(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth,
+                      const float* w_mean, const float* noise, const float* after, float* x,
+                      int32_t T, int32_t S, int32_t B, int32_t n, int32_t d, int32_t dout, float state_var, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

@@ -90,6 +90,8 @@ SIGNATURES = {
     "vjf_fixed_points": [_P] * 10 + [_I] * 5 + [_F, _F, _P],
     "vjf_smooth_plan": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_smooth": [_P] * 12 + [_I] * 5 + [_F, _P],
+    "vjf_smooth_sample_plan": [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(C.c_int64)],
+    "vjf_smooth_sample": [_P] * 9 + [_I] * 6 + [_F, _P],
     "vjf_rls_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_blr_rls": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_kalman_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],

@@ -40,6 +40,7 @@
 #include "vjf_host_tangent.h"
 #include "vjf_host_fixed_point.h"
 #include "vjf_host_smooth.h"
+#include "vjf_host_smooth_sample.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -574,6 +575,35 @@ int vjf_smooth(const float* mu, const float* logvar, const float* u, const float
     a.after_cov = after_cov; a.mean = mean; a.var = var; a.cov = cov; a.cov0 = cov0; a.T = T; a.B = B; a.n = n; a.d = d; a.dout = dout;
     a.rsq = 1.f / sqrtf(state_var);
     return smooth_run(a, p, (hipStream_t)stream);
+}
+
+int vjf_smooth_sample_plan(int32_t n, int32_t d, int32_t dout, int32_t S, int32_t* members_per_workgroup, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout || S < 1) return fail(-20, "vjf_smooth_sample_plan: bad shape (n=%d d=%d dout=%d S=%d)", n, d, dout, S);
+    const SmsPlan p = sms_plan(n, d, dout, S, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_int("VJF_SMS_MEMBERS"));
+    if (!p.fits)
+        return fail(-11, "vjf_smooth_sample_plan: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_SMS_MAXDOUT ? "dout <= 32 (VJF_SMS_MAXDOUT)" : "one workgroup's LDS");
+    if (members_per_workgroup) *members_per_workgroup = p.sc;
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_smooth_sample(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth,
+                      const float* w_mean, const float* noise, const float* after, float* x, int32_t T, int32_t S, int32_t B, int32_t n,
+                      int32_t d, int32_t dout, float state_var, void* stream) {
+    if (!mu || !logvar || !centroid || !logwidth || !w_mean || !noise || !x) return fail(-1, "vjf_smooth_sample: null tensor");
+    if (T < 1 || S < 1 || B < 1 || n < 1 || dout < 1 || d < dout || !(state_var > 0.f && state_var < INFINITY))
+        return fail(-20, "vjf_smooth_sample: bad shape (T=%d S=%d B=%d n=%d d=%d dout=%d state_var=%g)", T, S, B, n, d, dout, (double)state_var);
+    if (d > dout && !u && (T > 1 || after)) return fail(-21, "vjf_smooth_sample: u is required when d > dout");
+    const SmsPlan p = sms_plan(n, d, dout, S, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_int("VJF_SMS_MEMBERS"));
+    if (!p.fits)
+        return fail(-11, "vjf_smooth_sample: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_SMS_MAXDOUT ? "dout <= 32 (VJF_SMS_MAXDOUT)" : "one workgroup's LDS");
+    if ((S + p.sc - 1) / p.sc > 65535) return fail(-11, "vjf_smooth_sample: S=%d beyond 65535 chunks of %d members", S, p.sc);
+    VjfSmsArgs a{};
+    a.mu = mu; a.lv = logvar; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.z = noise; a.after = after;
+    a.x = x; a.T = T; a.S = S; a.B = B; a.n = n; a.d = d; a.dout = dout; a.rsq = 1.f / sqrtf(state_var);
+    return smooth_sample_run(a, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

@@ -19,6 +19,8 @@
 // depends on data.  A trial whose inputs are not finite, or whose factor has a pivot that is not positive and finite, has NaN written
 // over its carried moments: they stay NaN down to row 0, and no other trial sees them.
 // Workgroups are independent: no cooperative launch, no hand-off, no scratch, no atomics.  Included by vjf_host_smooth.h.
+// vjf_smooth_sample_kernel.h has its own copy of `factor` and of the scale, factor and gain phases, statement for statement; these
+// stay where they are so that this kernel's assembly does not move (profiles/sampler_isa.txt).  Whoever changes one changes both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_flow_eval.h"           // flow_evaluate; the x step's FcTile, fc_stage, fc_u_ahead / fc_u_advance

@@ -114,6 +114,11 @@ class SmoothResult(namedtuple('SmoothResult', ['mean', 'var', 'cov', 'head'])):
         return Gaussian(self.mean, self.var.log())
 
 
+# what RBFDS.sample_posterior / VJF.sample_posterior return: the joint draws x (S, T, B, xdim) and head = x[:, 0] (S, B, xdim), what a
+# call on the rows before these takes as `after`
+PosteriorSamples = namedtuple('PosteriorSamples', ['x', 'head'])
+
+
 class LinearDecoder(Module):
     """vjf/model.py:21-42"""
     def __init__(self, xdim: int, ydim: int):
@@ -588,6 +593,73 @@ class RBFDS(Module):
             raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
         N.check(rc, "vjf_smooth")
         return SmoothResult(mean, var, cov, (mean[0], cov0))
+
+    def sample_posterior(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, n_sample: int = 16, *,
+                         state_var: float = None, noise: Tensor = None, after: Tensor = None) -> PosteriorSamples:
+        """`n_sample` joint draws per trial from the smoothed posterior of a filtered sequence as ONE C-ABI call (vjf_smooth_sample):
+        backward sampling with the learned mean map and its Jacobian, the contract stated in include/vjf_hip.h.  Each row is
+        conditioned on the draw of the row behind it; the gain and the factor of a row depend on the filtered row alone and are shared
+        by the members.  The draws are exactly Gaussian: their row means and covariances are `smooth`'s, and whole trajectories carry
+        the posterior's correlation across rows, which the marginals of `smooth` cannot.
+        :param q, u, state_var: as `smooth` (a Gaussian or a (mu, logvar) pair of (T, B, xdim), a (T, xdim) pair is one trial; u the
+            array that went into the filter, with `after` one row more; the default state_var reads one scalar from the device)
+        :param n_sample: S, the draws per trial
+        :param noise: (S, T, B, xdim) standard-normal values, used as they are.  Not given, they follow the owning model's `noise`:
+            "device" is one torch.randn of that shape on the GPU, "reference" one randn of that shape on the CPU generator in the
+            default dtype, so a seed fixes the draws
+        :param after: (S, B, xdim), the draws of the row behind the last one, such as a previous result's `head`: drawing rows [k, T)
+            first and rows [0, k) with after = that head (and the same noise rows) second gives the bits of one call
+        :return: PosteriorSamples(x (S, T, B, xdim), head = x[:, 0]).  A trial with a non-finite input at some row has NaN in every
+            member from that row back to row 0.
+        Reads the model's state and writes none; no scratch."""
+        mu, lv = (q.mean, q.logvar) if isinstance(q, Gaussian) else q
+        mu, lv = dev32(mu, ndim2=False), dev32(lv, ndim2=False)
+        mu, lv = (t[:, None, :] if t.ndim == 2 else t for t in (mu, lv))        # (T, xdim): one trial
+        assert mu.ndim == 3 and lv.shape == mu.shape, f"q is {tuple(mu.shape)} and {tuple(lv.shape)}, expected two (T, B, xdim)"
+        mu, lv = mu.contiguous(), lv.contiguous()
+        T, B, dout = mu.shape
+        assert T >= 1, 'q must have at least one row'
+        assert dout == self.velocity.n_output, f"q has {dout} columns, expected xdim={self.velocity.n_output}"
+        S = int(n_sample)
+        if S < 1:
+            raise ValueError(f"n_sample must be at least 1, got {n_sample}")
+        if dout > SM_MAX_XDIM:
+            raise NotImplementedError(f"sample_posterior covers xdim <= {SM_MAX_XDIM}, this model has xdim = {dout}")
+        state_var = float(self.logvar.exp()) if state_var is None else float(state_var)
+        if not 0. < state_var < float('inf'):
+            raise ValueError(f"state_var must be positive and finite, got {state_var}")
+        if after is not None:
+            after = dev32(after, ndim2=False)
+            if after.ndim == 2 and B == 1:
+                after = after[:, None, :]
+            assert after.shape == (S, B, dout), f"after is {tuple(after.shape)}, expected {(S, B, dout)}"
+            after = after.contiguous()
+        if noise is None:
+            if self._noise_mode() == "reference":
+                noise = dev32(torch.randn(S, T, B, dout, dtype=torch.get_default_dtype()), ndim2=False)
+            else:
+                noise = torch.randn(S, T, B, dout, device=mu.device, dtype=torch.float32)
+        else:
+            noise = dev32(noise, ndim2=False)
+            if noise.ndim == 3 and B == 1:
+                noise = noise[:, :, None, :]
+            assert noise.shape == (S, T, B, dout), f"noise is {tuple(noise.shape)}, expected {(S, T, B, dout)}"
+            noise = noise.contiguous()
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        rows = T + (after is not None)
+        if d > dout and u is not None:
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == rows, f"u has {u.shape[0]} rows, expected {rows} (T{' + 1 with `after`' if after is not None else ''})"
+        u = self._tangent_u(u, rows, B)
+        x = torch.empty(S, T, B, dout, device=mu.device, dtype=torch.float32)
+        rc = N.lib().vjf_smooth_sample(N.ptr(mu), N.ptr(lv), N.ptr(u), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                                       N.ptr(vel.w_mean), N.ptr(noise), N.ptr(after), N.ptr(x), T, S, B, n, d, dout, state_var,
+                                       stream_ptr())
+        if rc == -11:                             # the shape is beyond the plan (vjf_smooth_sample_plan): nothing was launched
+            raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_smooth_sample")
+        return PosteriorSamples(x, x[:, 0])
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1276,3 +1348,10 @@ class VJF(Module):
         """The smoothed posterior q(x_t | y_1..T) of a filtered sequence -- what `filter_sequence` / `fit` returned -- in one native
         call (RBFDS.smooth has the arguments); `model.decoder(res.gaussian().mean)` gives the smoothed observations."""
         return self.transition.smooth(q, u, state_var=state_var, after=after, return_cov=return_cov)
+
+    def sample_posterior(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, n_sample: int = 16, *,
+                         state_var: float = None, noise: Tensor = None, after: Tensor = None) -> PosteriorSamples:
+        """`n_sample` joint draws per trial from the smoothed posterior of a filtered sequence -- whole trajectories, each row
+        conditioned on the draw behind it -- in one native call (RBFDS.sample_posterior has the arguments); `model.decoder(res.x)`
+        gives draws of the observations' means."""
+        return self.transition.sample_posterior(q, u, n_sample, state_var=state_var, noise=noise, after=after)
