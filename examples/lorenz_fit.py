@@ -2,7 +2,7 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--score 16] [--plot out.png]
 
 With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
 the +-2 sd band of the first latent at a few steps.  With --lyapunov N it prints the Lyapunov spectrum of the learned flow over N steps
@@ -12,7 +12,9 @@ its residual, the moduli of the eigenvalues of the Jacobian there and whether it
 sequence with the learned dynamics (`smooth`) and prints how far the smoothed means lie from the filtered ones and the mean filtered
 against the mean smoothed variance.  With --sample S it draws S whole trajectories from the smoothed posterior (`sample_posterior`)
 and prints, per latent dimension, the RMS of the draws' standard deviation against the smoothed one, the lag-one correlation of the
-draws, and the width of the band that holds 90 % of whole trajectories against the +-1.64 sd band of the marginals.
+draws, and the width of the band that holds 90 % of whole trajectories against the +-1.64 sd band of the marginals.  With --score K it
+scores the learned dynamics (`score_forecast`): per horizon h = 1 .. K the R^2 of the h-step-ahead prediction of the latent state and of
+the observations over the record, and the skill against persistence.
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -39,6 +41,7 @@ def main(argv=None):
     ap.add_argument("--fixed-points", type=int, default=0, help="starts of the search for fixed points of the learned flow (0: skip it), e.g. 64")
     ap.add_argument("--smooth", action="store_true", help="smooth the filtered sequence with the learned dynamics")
     ap.add_argument("--sample", type=int, default=0, help="joint draws from the smoothed posterior (0: skip them), e.g. 64")
+    ap.add_argument("--score", type=int, default=0, help="horizons of the k-step-ahead prediction error over the record (0: skip it), e.g. 16")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -107,6 +110,14 @@ def main(argv=None):
             lag = float((dev[:, 1:, k] * dev[:, :-1, k]).mean())
             print(f"sample: x{k + 1}  RMS relative error of the draws' sd against the smoothed sd = {rms:.3f}   lag-one correlation = {lag:+.3f}"
                   f"   90 % of whole paths stay within +-{float(reach[:, k].quantile(0.9)):.2f} sd (marginal band: +-1.64 sd)")
+    if a.score > 0:
+        # how good the learned dynamics are: from every row of the filtered record the mean map rolled h = 1 .. K steps, against what the
+        # filter found and what was observed h rows on, the whole record in one native call
+        sc = model.score_forecast(m, y, n_step=a.score)
+        r2x, r2y, skx, sky = (v.cpu() for v in (sc.r2_x(), sc.r2_y(), sc.skill_x(), sc.skill_y()))
+        for h in range(1, a.score + 1):
+            print(f"score: h = {h:3d}  n = {int(sc.n[h]):6d}  R2 x = {float(r2x[h]):+.4f}  y = {float(r2y[h]):+.4f}"
+                  f"   skill against persistence x = {float(skx[h]):+.4f}  y = {float(sky[h]):+.4f}")
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

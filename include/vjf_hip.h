@@ -401,6 +401,41 @@ int vjf_smooth_sample_plan(int32_t n, int32_t d, int32_t dout, int32_t S, int32_
 int vjf_smooth_sample(const float* mu, const float* logvar, const float* u, const float* centroid, const float* logwidth,
                       const float* w_mean, const float* noise, const float* after, float* x,
                       int32_t T, int32_t S, int32_t B, int32_t n, int32_t d, int32_t dout, float state_var, void* stream);
+/* Scoring predictions: the k-step-ahead prediction error of the mean map f(x, u) = x + Phi([x, u]) w_mean over a filtered record, the
+ * whole record as one call, fp32 with fp64 totals.  mu (T,B,dout): the filtered means; y (T,B,dy) or NULL with the decoder dec_W
+ * (dy,dout), dec_b (dy); u (T,B,du) or NULL (du = d - dout), the array that went into the filter: the transition from row t to row
+ * t + 1 reads u[t + 1], u[0] is never read.  For every origin t and trial b:
+ *   xh_0 = mu[t,b],  xh_j = xh_{j-1} + Phi([xh_{j-1}, u[t+j,b]]) w_mean  for j = 1 .. K;   horizon h is valid iff t + h <= T - 1.
+ * Outputs, float64, horizon h = 0 .. K on the first axis, sums over the valid (t, b):
+ *   sse_x (K+1,dout) = sum (xh_h - mu[t+h])^2, row 0 exactly 0;   base_x (K+1,dout) = sum (mu[t] - mu[t+h])^2, persistence;
+ *   with y, poisson == 0:  sse_y (K+1,dy) = sum (xh_h dec_W^T + dec_b - y[t+h])^2 (row 0: the filter's own reconstruction error),
+ *                          base_y the same with xh_0 in place of xh_h;
+ *   with y, poisson != 0:  sse_y = sum (exp(ec) - y[t+h] ec), ec = min(eta, 10), eta = xh_h dec_W^T + dec_b (PoissonLikelihood.loss,
+ *                          vjf/likelihood.py:60, without log y!, per output column), base_y the same for xh_0;
+ *   pred (K,T,B,dout) float32 or NULL: pred[h-1,t,b] = xh_h where valid, NaN elsewhere.
+ * The counts max(T - h, 0) B are the caller's arithmetic; a horizon beyond the record has sums exactly 0.
+ * Summation order (the results have defined bits).  The record is handled flattened: start r = t B + b is compared at horizon h with
+ * row r + h B and step j reads row r + j B of u.  Tile i holds the starts 16 i .. 16 i + 15 and may straddle origins.  Per tile,
+ * horizon and column the valid starts' terms are added in start order in fp32, each term rounded on its own (the difference, its
+ * square, then the sum: three roundings; Poisson: exp, the product, their difference, the sum) -- a partial in `scratch`; a second
+ * kernel adds the tiles' partials in tile order in fp64.  No floating-point atomics.  So the bits do not depend on the stream, on
+ * VJF_KS_CHUNK (tiles per chunk; default: partials within 32 MiB) or on the forms of the kernels (VJF_FC_CENTROID_LDS,
+ * VJF_FC_LOOKAHEAD); they DO depend on the order of the trials.  pred of a start depends on that start's inputs alone and is, bit for
+ * bit, vjf_forecast_seq from mu[t] with zero weight noise.  A start whose horizon has run out of record keeps stepping on the control
+ * input it read last and is masked out.  Asynchronous on `stream`, no host synchronisation; reads the state tensors, writes none.
+ * scratch: >= vjf_kstep_score_scratch_size bytes (dy = 0 without y), one call at a time per scratch.
+ * -1 null tensor, -20 bad shape (also T < 1, K < 1, y without a decoder), -21 u missing with d > dout, -11 the shape is beyond one
+ * workgroup's LDS (the message names the limit): all before the first launch.
+ * vjf_kstep_score_plan: pure arithmetic, callable without a GPU: the dynamic LDS of a workgroup, the tiles of the record, the tiles
+ * per chunk and the forms (bit 0 centroids in LDS, bit 1 w_mean's operands in registers, bit 2 decoder in LDS); any pointer may be
+ * NULL; -11 / -20 as the call. */
+int vjf_kstep_score_scratch_size(int32_t T, int32_t B, int32_t K, int32_t dout, int32_t dy, int64_t* bytes);
+int vjf_kstep_score_plan(int32_t T, int32_t B, int32_t K, int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes,
+                         int64_t* tiles, int64_t* tiles_per_chunk, int32_t* forms);
+int vjf_kstep_score(const float* mu, const float* y, const float* u, const float* centroid, const float* logwidth,
+                    const float* w_mean, const float* dec_W, const float* dec_b, double* sse_x, double* base_x, double* sse_y,
+                    double* base_y, float* pred, void* scratch, int32_t T, int32_t B, int32_t K, int32_t n, int32_t d, int32_t dout,
+                    int32_t dy, int32_t poisson, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

@@ -92,6 +92,9 @@ SIGNATURES = {
     "vjf_smooth": [_P] * 12 + [_I] * 5 + [_F, _P],
     "vjf_smooth_sample_plan": [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(C.c_int64)],
     "vjf_smooth_sample": [_P] * 9 + [_I] * 6 + [_F, _P],
+    "vjf_kstep_score_scratch_size": [_I, _I, _I, _I, _I, C.POINTER(C.c_int64)],
+    "vjf_kstep_score_plan": [_I] * 7 + [C.POINTER(C.c_int64)] * 3 + [C.POINTER(_I)],
+    "vjf_kstep_score": [_P] * 14 + [_I] * 8 + [_P],
     "vjf_rls_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_blr_rls": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_kalman_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],

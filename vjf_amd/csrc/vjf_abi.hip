@@ -41,6 +41,7 @@
 #include "vjf_host_fixed_point.h"
 #include "vjf_host_smooth.h"
 #include "vjf_host_smooth_sample.h"
+#include "vjf_host_kstep.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -604,6 +605,50 @@ int vjf_smooth_sample(const float* mu, const float* logvar, const float* u, cons
     a.mu = mu; a.lv = logvar; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.z = noise; a.after = after;
     a.x = x; a.T = T; a.S = S; a.B = B; a.n = n; a.d = d; a.dout = dout; a.rsq = 1.f / sqrtf(state_var);
     return smooth_sample_run(a, p, (hipStream_t)stream);
+}
+
+int vjf_kstep_score_scratch_size(int32_t T, int32_t B, int32_t K, int32_t dout, int32_t dy, int64_t* bytes) {
+    if (!bytes || T < 1 || B < 1 || K < 1 || dout < 1 || dy < 0 || ((int64_t)K + 1) * (2 * (int64_t)dout + 2 * (int64_t)dy) > (1 << 28))
+        return fail(-20, "vjf_kstep_score_scratch_size: bad argument");
+    *bytes = (int64_t)ks_scratch_bytes(T, B, K, dout, dy);
+    return 0;
+}
+
+int vjf_kstep_score_plan(int32_t T, int32_t B, int32_t K, int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes,
+                         int64_t* tiles, int64_t* tiles_per_chunk, int32_t* forms) {
+    if (T < 1 || B < 1 || K < 1 || n < 1 || dout < 1 || d < dout || dy < 0 || ((int64_t)K + 1) * (2 * (int64_t)dout + 2 * (int64_t)dy) > (1 << 28))
+        return fail(-20, "vjf_kstep_score_plan: bad shape (T=%d B=%d K=%d n=%d d=%d dout=%d dy=%d)", T, B, K, n, d, dout, dy);
+    const KsPlan p = ks_plan(T, B, K, n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_FC_LOOKAHEAD"), fc_env_int("VJF_KS_CHUNK"));
+    if (!p.fits)
+        return fail(-11, "vjf_kstep_score_plan: n=%d, d=%d, dout=%d, dy=%d beyond one workgroup's LDS (%zu bytes)", n, d, dout, dy, kMaxLds - 1024);
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    if (tiles) *tiles = p.tiles;
+    if (tiles_per_chunk) *tiles_per_chunk = p.per_chunk;
+    if (forms) *forms = (p.cl ? 1 : 0) | (p.la ? 2 : 0) | (p.dl ? 4 : 0);
+    return 0;
+}
+
+int vjf_kstep_score(const float* mu, const float* y, const float* u, const float* centroid, const float* logwidth, const float* w_mean,
+                    const float* dec_W, const float* dec_b, double* sse_x, double* base_x, double* sse_y, double* base_y, float* pred,
+                    void* scratch, int32_t T, int32_t B, int32_t K, int32_t n, int32_t d, int32_t dout, int32_t dy, int32_t poisson,
+                    void* stream) {
+    if (!mu || !centroid || !logwidth || !w_mean || !sse_x || !base_x || !scratch || (y && (!sse_y || !base_y)))
+        return fail(-1, "vjf_kstep_score: null tensor");
+    if (y && (!dec_W || !dec_b)) return fail(-20, "vjf_kstep_score: y without a decoder");
+    if (!y) dy = 0;
+    if (T < 1 || B < 1 || K < 1 || n < 1 || dout < 1 || d < dout || (y && dy < 1) ||
+        ((int64_t)K + 1) * (2 * (int64_t)dout + 2 * (int64_t)dy) > (1 << 28))
+        return fail(-20, "vjf_kstep_score: bad shape (T=%d B=%d K=%d n=%d d=%d dout=%d dy=%d)", T, B, K, n, d, dout, dy);
+    if (d > dout && !u) return fail(-21, "vjf_kstep_score: u is required when d > dout");
+    const KsPlan p = ks_plan(T, B, K, n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_FC_LOOKAHEAD"), fc_env_int("VJF_KS_CHUNK"));
+    if (!p.fits)
+        return fail(-11, "vjf_kstep_score: n=%d, d=%d, dout=%d, dy=%d beyond one workgroup's LDS (%zu bytes)", n, d, dout, dy, kMaxLds - 1024);
+    VjfKsArgs a{};
+    a.mu = mu; a.y = y; a.u = d > dout ? u : nullptr; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.dec_W = dec_W; a.dec_b = dec_b;
+    a.pred = pred; a.R = (long long)T * B; a.B = B; a.K = K; a.n = n; a.d = d; a.dout = dout; a.dy = dy; a.poisson = poisson != 0;
+    VjfKsFoldArgs f{};
+    f.sse_x = sse_x; f.base_x = base_x; f.sse_y = sse_y; f.base_y = base_y;
+    return kstep_run(a, f, scratch, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

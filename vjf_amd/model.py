@@ -119,6 +119,70 @@ class SmoothResult(namedtuple('SmoothResult', ['mean', 'var', 'cov', 'head'])):
 PosteriorSamples = namedtuple('PosteriorSamples', ['x', 'head'])
 
 
+class ForecastScore(namedtuple('ForecastScore', ['n', 'sse_x', 'base_x', 'sse_y', 'base_y', 'sst_x', 'sst_y', 'pred', 'kind'])):
+    """What RBFDS.score_forecast / VJF.score_forecast return, every array with the horizon h = 0 .. n_step on its first axis and float64
+    unless said otherwise, all on the record's device: n (n_step + 1,) int64, the (origin, trial) pairs whose horizon h lies inside the record, max(T - h, 0) B;
+    sse_x (.., xdim), the summed squared error of the h-step prediction against the filtered mean h rows on (row 0 is exactly 0);
+    base_x, the same for persistence (the origin's own mean as the prediction); sse_y, base_y (.., ydim) or None without y: under the
+    Gaussian likelihood the summed squared error of the decoded prediction against y (row 0: the filter's own reconstruction error),
+    under the Poisson likelihood the summed negative log-likelihood exp(min(eta, 10)) - y min(eta, 10) (without log y!); sst_x, sst_y,
+    the targets' total sum of squares about their mean over the valid rows (sst_y is None under Poisson); pred (n_step, T, B, xdim)
+    float32 or None, the h-step predictions themselves, NaN where t + h is beyond the record; kind: "gaussian", "poisson" or None
+    (no y).  A horizon beyond the record has n = 0, sums 0 and NaN from the methods."""
+    __slots__ = ()
+
+    @staticmethod
+    def _ratio(num, den):
+        return 1. - num.sum(-1) / den.sum(-1)
+
+    def r2_x(self) -> Tensor:
+        """1 - sum sse_x / sum sst_x per horizon (sums over the columns)."""
+        return self._ratio(self.sse_x, self.sst_x)
+
+    def r2_y(self) -> Tensor:
+        """1 - sum sse_y / sum sst_y per horizon; Gaussian likelihood only."""
+        if self.sse_y is None or self.sst_y is None:
+            raise ValueError("r2_y needs y and the Gaussian likelihood" if self.kind != "poisson" else
+                             "r2_y is not defined under the Poisson likelihood: use skill_y")
+        return self._ratio(self.sse_y, self.sst_y)
+
+    def skill_x(self) -> Tensor:
+        """1 - sum sse_x / sum base_x per horizon: above 0 where the learned map beats persistence."""
+        return self._ratio(self.sse_x, self.base_x)
+
+    def skill_y(self) -> Tensor:
+        """1 - score / base per horizon for the observations (squared error, or the Poisson negative log-likelihood)."""
+        if self.sse_y is None:
+            raise ValueError("skill_y needs y")
+        return self._ratio(self.sse_y, self.base_y)
+
+    def mse_x(self) -> Tensor:
+        """sse_x per (pair, column), per horizon."""
+        return self.sse_x.sum(-1) / (self.n.to(self.sse_x.device, torch.float64) * self.sse_x.shape[-1])
+
+    def mse_y(self) -> Tensor:
+        """sse_y per (pair, column), per horizon (under Poisson: the mean negative log-likelihood)."""
+        if self.sse_y is None:
+            raise ValueError("mse_y needs y")
+        return self.sse_y.sum(-1) / (self.n.to(self.sse_y.device, torch.float64) * self.sse_y.shape[-1])
+
+
+def _suffix_sst(v: Tensor, K: int) -> Tensor:
+    """(K + 1, dim) float64: per horizon h the sum of squares of rows h .. T - 1 of v (T, B, dim) about their own mean, from suffix
+    sums of the values shifted by the overall mean; 0 for h >= T."""
+    v = v.double()
+    T, B, dim = v.shape
+    v = v - v.mean((0, 1))
+    # (the scan runs along the last axis of a contiguous (dim, T) array: torch's scan along an outer axis is serial per column)
+    s1 = v.sum(1).t().contiguous().flip(1).cumsum(1).flip(1).t()
+    s2 = (v * v).sum(1).t().contiguous().flip(1).cumsum(1).flip(1).t()
+    out = torch.zeros(K + 1, dim, dtype=torch.float64, device=v.device)
+    m = min(K + 1, T)
+    cnt = ((T - torch.arange(m, device=v.device)) * B).to(torch.float64)[:, None]
+    out[:m] = (s2[:m] - s1[:m] * s1[:m] / cnt).clamp_(min=0.)
+    return out
+
+
 class LinearDecoder(Module):
     """vjf/model.py:21-42"""
     def __init__(self, xdim: int, ydim: int):
@@ -182,6 +246,7 @@ class RBFDS(Module):
         self._n_sample = 0
         self._fc_scratch = None
         self._fe_scratch = None
+        self._ks_scratch = None
         object.__setattr__(self, '_owner', None)
         self._shrink = 1.
         self.shrink = shrink
@@ -660,6 +725,70 @@ class RBFDS(Module):
             raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
         N.check(rc, "vjf_smooth_sample")
         return PosteriorSamples(x, x[:, 0])
+
+    def score_forecast(self, mu: Tensor, u: Tensor = None, n_step: int = 8, *, return_pred: bool = False) -> ForecastScore:
+        """The k-step-ahead prediction error of the mean map over a filtered record as ONE C-ABI call (vjf_kstep_score; the contract
+        and the summation order are stated in include/vjf_hip.h): from every row t the map x <- x + Phi([x, u]) w_mean is rolled
+        h = 1 .. n_step steps from mu[t] and compared with mu[t + h], summed per horizon and column over the pairs with t + h inside
+        the record, beside the same sums for persistence.
+        :param mu: the filtered means (T, B, xdim) -- what `filter_sequence` / `fit` return; (T, xdim) is one trial
+        :param u: (T, B, udim), the array that went into the filter (the step from row t to t + 1 reads u[t + 1]; u[0] is never read)
+        :param return_pred: also return the predictions (n_step, T, B, xdim) -- for plots, not for large records
+        :return: ForecastScore without the y fields.  The sums are deterministic, bit for bit, and depend on the order of the trials
+            (not on the stream or the chunking).
+        Asynchronous; reads the model's state and writes none.  The partial sums live in ONE bounded scratch tensor kept on this
+        module (like `_fc_scratch`): run one call per model at a time."""
+        return self._score_forecast(None, None, mu, None, u, n_step, return_pred)
+
+    def _score_forecast(self, decoder, kind, mu, y, u, n_step, return_pred):
+        K = int(n_step)
+        if K < 1:
+            raise ValueError(f"n_step must be at least 1, got {n_step}")
+        mu = dev32(mu, ndim2=False)
+        if mu.ndim == 2:
+            mu = mu[:, None, :]                              # (T, xdim): one trial
+        assert mu.ndim == 3, f"mu is {tuple(mu.shape)}, expected (T, B, xdim)"
+        mu = mu.contiguous()
+        T, B, dout = mu.shape
+        assert T >= 1, 'mu must have at least one row'
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        assert dout == vel.n_output, f"mu has {dout} columns, expected xdim={vel.n_output}"
+        if d > dout and u is not None:
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == T, f"u has {u.shape[0]} rows, expected {T}"
+        u = self._tangent_u(u, T, B)
+        W = b = None
+        dy = 0
+        if y is not None:
+            W, b = decoder.decode.weight, decoder.decode.bias
+            dy = W.shape[0]
+            y = dev32(y, ndim2=False)
+            if y.ndim == 2 and B == 1:
+                y = y[:, None, :]
+            assert y.shape == (T, B, dy), f"y is {tuple(y.shape)}, expected {(T, B, dy)}"
+            y = y.contiguous()
+        else:
+            kind = None
+        L = N.lib()
+        rc = L.vjf_kstep_score_plan(T, B, K, n, d, dout, dy, None, None, None, None)
+        if rc == -11:                             # the shape is beyond one workgroup's LDS: nothing was launched
+            raise NotImplementedError(L.vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_kstep_score_plan")
+        self._ks_scratch = kept_scratch(self._ks_scratch, mu.device, L.vjf_kstep_score_scratch_size, T, B, K, dout, dy)
+        new64 = lambda *shape: torch.empty(*shape, device=mu.device, dtype=torch.float64)    # noqa: E731
+        sse_x, base_x = new64(K + 1, dout), new64(K + 1, dout)
+        sse_y, base_y = (new64(K + 1, dy), new64(K + 1, dy)) if dy else (None, None)
+        pred = torch.empty(K, T, B, dout, device=mu.device, dtype=torch.float32) if return_pred else None
+        rc = L.vjf_kstep_score(N.ptr(mu), N.ptr(y), N.ptr(u), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                               N.ptr(vel.w_mean), N.ptr(W), N.ptr(b), N.ptr(sse_x), N.ptr(base_x), N.ptr(sse_y), N.ptr(base_y),
+                               N.ptr(pred), N.ptr(self._ks_scratch), T, B, K, n, d, dout, dy, int(kind == "poisson"), stream_ptr())
+        if rc == -11:
+            raise NotImplementedError(L.vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_kstep_score")
+        cnt = (T - torch.arange(K + 1, device=mu.device)).clamp_(min=0) * B
+        sst_y = _suffix_sst(y, K) if dy and kind != "poisson" else None
+        return ForecastScore(cnt, sse_x, base_x, sse_y, base_y, _suffix_sst(mu, K), sst_y, pred, kind)
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1355,3 +1484,16 @@ class VJF(Module):
         conditioned on the draw behind it -- in one native call (RBFDS.sample_posterior has the arguments); `model.decoder(res.x)`
         gives draws of the observations' means."""
         return self.transition.sample_posterior(q, u, n_sample, state_var=state_var, noise=noise, after=after)
+
+    def score_forecast(self, q: Union[Gaussian, Tuple[Tensor, Tensor], Tensor], y: Tensor = None, u: Tensor = None, n_step: int = 8, *,
+                       return_pred: bool = False) -> ForecastScore:
+        """How good the learned dynamics are: the k-step-ahead prediction error over a filtered record -- what `filter_sequence` /
+        `fit` returned -- in one native call (RBFDS.score_forecast has the arguments and the contract).
+        :param q: the filtered posterior: a Gaussian, a (mu, logvar) pair of tensors (tuple or list) or the means themselves, (T, B, xdim);
+            (T, xdim) is one trial
+        :param y: (T, B, ydim), the observations: the predictions are also decoded on chip and scored against them, by squared error
+            under the Gaussian likelihood and by the Poisson negative log-likelihood (without log y!) under the Poisson one
+        :return: ForecastScore; `.r2_x()`, `.r2_y()`, `.skill_x()`, `.skill_y()`, `.mse_x()`, `.mse_y()` reduce it per horizon."""
+        mu = q.mean if isinstance(q, Gaussian) else (q[0] if isinstance(q, (tuple, list)) and len(q) == 2 and isinstance(q[0], Tensor) else q)
+        kind = "poisson" if isinstance(self.likelihood, PoissonLikelihood) else "gaussian"
+        return self.transition._score_forecast(self.decoder, kind, mu, y, u, n_step, return_pred)
