@@ -2,7 +2,7 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--score 16] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--score 16] [--ekf] [--plot out.png]
 
 With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
 the +-2 sd band of the first latent at a few steps.  With --lyapunov N it prints the Lyapunov spectrum of the learned flow over N steps
@@ -14,7 +14,8 @@ against the mean smoothed variance.  With --sample S it draws S whole trajectori
 and prints, per latent dimension, the RMS of the draws' standard deviation against the smoothed one, the lag-one correlation of the
 draws, and the width of the band that holds 90 % of whole trajectories against the +-1.64 sd band of the marginals.  With --score K it
 scores the learned dynamics (`score_forecast`): per horizon h = 1 .. K the R^2 of the h-step-ahead prediction of the latent state and of
-the observations over the record, and the skill against persistence.
+the observations over the record, and the skill against persistence.  With --ekf it runs the model's own extended Kalman filter over
+the record (`ekf`) and prints the evidence per row and the RMS distance between the recognition network's and the filter's means.
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -42,6 +43,7 @@ def main(argv=None):
     ap.add_argument("--smooth", action="store_true", help="smooth the filtered sequence with the learned dynamics")
     ap.add_argument("--sample", type=int, default=0, help="joint draws from the smoothed posterior (0: skip them), e.g. 64")
     ap.add_argument("--score", type=int, default=0, help="horizons of the k-step-ahead prediction error over the record (0: skip it), e.g. 16")
+    ap.add_argument("--ekf", action="store_true", help="the model's own extended Kalman filter over the record: evidence and means")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -118,6 +120,14 @@ def main(argv=None):
         for h in range(1, a.score + 1):
             print(f"score: h = {h:3d}  n = {int(sc.n[h]):6d}  R2 x = {float(r2x[h]):+.4f}  y = {float(r2y[h]):+.4f}"
                   f"   skill against persistence x = {float(skx[h]):+.4f}  y = {float(sky[h]):+.4f}")
+    if a.ekf:
+        # the model's own Bayesian filter, no recognition network: the extended Kalman filter of the learned flow, state noise, decoder
+        # and observation noise over the whole record in one native call -- the evidence log p(y_t | y_1..t-1) row by row, and how far
+        # the amortised posterior means lie from it
+        ek = model.ekf(y)
+        rms = float((ek.mean.cpu()[:, 0] - m).pow(2).sum(-1).mean().sqrt())
+        print(f"ekf: evidence per row = {float(ek.log_likelihood()[0]) / a.T:+.4f}   RMS |recognition - ekf mean| = {rms:.4f}"
+              f"   mean variance recognition {float(logvar.detach().exp().mean()):.3e} -> ekf {float(ek.var.mean()):.3e}")
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

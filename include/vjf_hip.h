@@ -436,6 +436,40 @@ int vjf_kstep_score(const float* mu, const float* y, const float* u, const float
                     const float* w_mean, const float* dec_W, const float* dec_b, double* sse_x, double* base_x, double* sse_y,
                     double* base_y, float* pred, void* scratch, int32_t T, int32_t B, int32_t K, int32_t n, int32_t d, int32_t dout,
                     int32_t dy, int32_t poisson, void* stream);
+/* Extended Kalman filter and model evidence: the Bayesian filter of the learned generative model itself -- the mean map
+ * f(x, u) = x + Phi([x, u]) w_mean with J = I + A its Jacobian, a scalar state-noise variance q = state_var, the linear decoder
+ * y = C x + b (C = dec_W (dy,dout), b = dec_b) and a scalar Gaussian observation variance r = obs_var -- over a whole record as one
+ * call, fp32 (replaces the per-step host loop of vjf/kalman.py:16-101).  u[t] drives the transition INTO row t, as in the filter;
+ * row 0 is predicted from the prior with u[0].  Gc = C^T C / r is formed once per call.  Carried per trial: m and the lower triangle
+ * of P.  Per row t:
+ *   1. predict:  g, A at (m, u_t), J = I + A;  m^- = m + g;  Ls Ls^T = P (Cholesky);  K = J Ls;  P^- = K K^T + q I = Lp Lp^T;
+ *   2. update:   M = I + Lp^T Gc Lp = Lm Lm^T (eigenvalues >= 1 whatever r and P^- are);  v = y - b - C m^-;  s = C^T v / r;
+ *                Lm Y = Lp^T;  P = Y^T Y (= Lp M^-1 Lp^T);  m = m^- + P s;
+ *   3. loglik[t] = -1/2 (dy log 2 pi + log det S + v^T S^-1 v),  S = C P^- C^T + r I,  through
+ *                log det S = dy log r + 2 sum log diag(Lm),   v^T S^-1 v = |y - b - C m|^2 / r + |Lp^-1 (m - m^-)|^2
+ *                (no dy x dy matrix, no difference of covariances, no subtraction of like terms);
+ *   4. a row with observed[t,b] == 0: the update runs with Gc = 0 and v = 0, so M = I and P = Lp Lp^T = P^- exactly, m = m^- and
+ *      loglik = 0 by per-trial selects; its y is never used in arithmetic and may hold anything (NaN included).
+ * y (T,B,dy); u (T,B,du) or NULL (du = d - dout); observed uint8 (T,B) or NULL (every row observed); the prior of the row before
+ * row 0: prior_mean (B,dout) with EITHER prior_logvar (B,dout), P = diag(exp(logvar)), OR prior_cov (B,dout,dout), its lower
+ * triangle is read -- exactly one of the two is non-NULL.  mean, var (T,B,dout): m and the diagonal of P; cov (T,B,dout,dout) or
+ * NULL: P written from its triangle -- exactly symmetric, its diagonal is var bit for bit; loglik (T,B); cov_last (B,dout,dout): P
+ * of the last row, always written.  Rows [0, k) first and rows [k, T) second with prior_mean = mean[k-1], prior_cov = cov[k-1] give
+ * the bits of the undivided call.  A trial with a non-finite m (the prior), u or observed y at row t, or with a pivot of a factor
+ * that is not positive and finite, has NaN in mean, var, cov and loglik from that row ON; its rows before and every other trial keep
+ * their bits.  No loop bound depends on data.  A trial's outputs depend on that trial's inputs alone, bit for bit (not on its row,
+ * the batch, the other trials of its tile, the stream, or where the planner puts the centroids and the decoder:
+ * VJF_FC_CENTROID_LDS, VJF_EKF_DECODER_LDS).  Asynchronous on `stream`, no host synchronisation, no scratch; reads the state
+ * tensors, writes none.
+ * -1 null tensor, -20 bad shape (also T < 1, dy < 1, state_var or obs_var not positive and finite, both or neither of prior_logvar /
+ * prior_cov), -21 u missing with d > dout, -11 dout > 32 or the shape is beyond one workgroup's LDS (every dout <= 24 with n <= 256
+ * and du <= 8 fits, whatever dy is): all before the first launch and before anything is written.
+ * vjf_ekf_plan: pure arithmetic, callable without a GPU: the dynamic LDS of a workgroup for these sizes; -11 / -20 as the call. */
+int vjf_ekf_plan(int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes);
+int vjf_ekf(const float* y, const float* u, const uint8_t* observed, const float* centroid, const float* logwidth,
+            const float* w_mean, const float* dec_W, const float* dec_b, const float* prior_mean, const float* prior_logvar,
+            const float* prior_cov, float* mean, float* var, float* cov, float* loglik, float* cov_last, int32_t T, int32_t B,
+            int32_t n, int32_t d, int32_t dout, int32_t dy, float state_var, float obs_var, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

@@ -42,6 +42,7 @@
 #include "vjf_host_smooth.h"
 #include "vjf_host_smooth_sample.h"
 #include "vjf_host_kstep.h"
+#include "vjf_host_ekf.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -649,6 +650,39 @@ int vjf_kstep_score(const float* mu, const float* y, const float* u, const float
     VjfKsFoldArgs f{};
     f.sse_x = sse_x; f.base_x = base_x; f.sse_y = sse_y; f.base_y = base_y;
     return kstep_run(a, f, scratch, p, (hipStream_t)stream);
+}
+
+int vjf_ekf_plan(int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout || dy < 1) return fail(-20, "vjf_ekf_plan: bad shape (n=%d d=%d dout=%d dy=%d)", n, d, dout, dy);
+    const EkfPlan p = ekf_plan(n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_EKF_DECODER_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_ekf_plan: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_EKF_MAXDOUT ? "dout <= 32 (VJF_EKF_MAXDOUT)" : "one workgroup's LDS");
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_ekf(const float* y, const float* u, const uint8_t* observed, const float* centroid, const float* logwidth, const float* w_mean,
+            const float* dec_W, const float* dec_b, const float* prior_mean, const float* prior_logvar, const float* prior_cov,
+            float* mean, float* var, float* cov, float* loglik, float* cov_last, int32_t T, int32_t B, int32_t n, int32_t d,
+            int32_t dout, int32_t dy, float state_var, float obs_var, void* stream) {
+    if (!y || !centroid || !logwidth || !w_mean || !dec_W || !dec_b || !prior_mean || !mean || !var || !loglik || !cov_last)
+        return fail(-1, "vjf_ekf: null tensor");
+    if (T < 1 || B < 1 || n < 1 || dout < 1 || d < dout || dy < 1 || !(state_var > 0.f && state_var < INFINITY) ||
+        !(obs_var > 0.f && obs_var < INFINITY) || !prior_logvar == !prior_cov)
+        return fail(-20, "vjf_ekf: bad shape (T=%d B=%d n=%d d=%d dout=%d dy=%d state_var=%g obs_var=%g%s)", T, B, n, d, dout, dy,
+                    (double)state_var, (double)obs_var, !prior_logvar == !prior_cov ? ", exactly one of prior_logvar / prior_cov is needed" : "");
+    if (d > dout && !u) return fail(-21, "vjf_ekf: u is required when d > dout");
+    const EkfPlan p = ekf_plan(n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_EKF_DECODER_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_ekf: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_EKF_MAXDOUT ? "dout <= 32 (VJF_EKF_MAXDOUT)" : "one workgroup's LDS");
+    VjfEkfArgs a{};
+    a.y = y; a.u = d > dout ? u : nullptr; a.obs = observed; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.dec_W = dec_W;
+    a.dec_b = dec_b; a.prior_mean = prior_mean; a.prior_lv = prior_logvar; a.prior_cov = prior_cov; a.mean = mean; a.var = var;
+    a.cov = cov; a.ll = loglik; a.cov_last = cov_last; a.T = T; a.B = B; a.n = n; a.d = d; a.dout = dout; a.dy = dy; a.q = state_var;
+    a.r = obs_var;
+    return ekf_run(a, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

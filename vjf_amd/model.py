@@ -76,6 +76,7 @@ ForecastEnsemble = namedtuple('ForecastEnsemble', ['x_mean', 'x_var', 'y_mean', 
 LyapunovResult = namedtuple('LyapunovResult', ['exponents', 'x', 'q', 'log_stretch'])
 FP_MAX_XDIM = 32                         # VJF_FP_MAXDOUT of vjf_fixed_points
 SM_MAX_XDIM = 32                         # VJF_SM_MAXDOUT of vjf_smooth
+EKF_MAX_XDIM = 32                        # VJF_EKF_MAXDOUT of vjf_ekf
 
 
 class FixedPointResult(namedtuple('FixedPointResult', ['x', 'residual', 'converged', 'n_iter', 'jacobian'])):
@@ -112,6 +113,23 @@ class SmoothResult(namedtuple('SmoothResult', ['mean', 'var', 'cov', 'head'])):
     def gaussian(self) -> Gaussian:
         """The smoothed marginals as the filter returns its posterior: Gaussian(mean, log var), e.g. for `model.decoder`."""
         return Gaussian(self.mean, self.var.log())
+
+
+class EKFResult(namedtuple('EKFResult', ['mean', 'var', 'cov', 'loglik', 'head'])):
+    """What VJF.ekf returns: the filtered means (T, B, xdim) of the model's own extended Kalman filter, the marginal variances var
+    (T, B, xdim), the full covariances cov (T, B, xdim, xdim) or None, the row log-likelihoods loglik (T, B) = log p(y_t | y_1..t-1)
+    (0 where a row is not observed) and head = (mean[-1], cov of the last row (B, xdim, xdim)): what a call on the following rows
+    takes as `before`."""
+    __slots__ = ()
+
+    def gaussian(self) -> Gaussian:
+        """The filtered marginals as `filter_sequence` returns its posterior: the diagonal Gaussian(mean, log var).  `smooth` accepts
+        it -- and then treats the filtered covariance as diagonal: the off-diagonal part of `cov` is dropped."""
+        return Gaussian(self.mean, self.var.log())
+
+    def log_likelihood(self) -> Tensor:
+        """The model evidence log p(y_1..T) per trial (B,), float64: the rows of `loglik` added up in float64."""
+        return self.loglik.double().sum(dim=0)
 
 
 # what RBFDS.sample_posterior / VJF.sample_posterior return: the joint draws x (S, T, B, xdim) and head = x[:, 0] (S, B, xdim), what a
@@ -789,6 +807,57 @@ class RBFDS(Module):
         cnt = (T - torch.arange(K + 1, device=mu.device)).clamp_(min=0) * B
         sst_y = _suffix_sst(y, K) if dy and kind != "poisson" else None
         return ForecastScore(cnt, sse_x, base_x, sse_y, base_y, _suffix_sst(mu, K), sst_y, pred, kind)
+
+    def _ekf(self, decoder, y, u, prior_mean, prior_logvar, prior_cov, state_var, obs_var, observed, return_cov):
+        """VJF.ekf behind its choice of prior and variances: the coercions, the refusals and the one call (vjf_ekf)."""
+        W, b = decoder.decode.weight, decoder.decode.bias
+        dy, dout = W.shape
+        y = dev32(y, ndim2=False)
+        if y.ndim == 2:
+            y = y[:, None, :]                                # (T, ydim): one trial
+        assert y.ndim == 3 and y.shape[2] == dy, f"y is {tuple(y.shape)}, expected (T, B, {dy})"
+        y = y.contiguous()
+        T, B = y.shape[:2]
+        assert T >= 1, 'y must have at least one row'
+        if dout > EKF_MAX_XDIM:
+            raise NotImplementedError(f"ekf covers xdim <= {EKF_MAX_XDIM}, this model has xdim = {dout}")
+        for name, v in (("state_var", state_var), ("obs_var", obs_var)):
+            if not 0. < v < float('inf'):
+                raise ValueError(f"{name} must be positive and finite, got {v}")
+        prior_mean = dev32(prior_mean)
+        assert prior_mean.shape == (B, dout), f"the prior mean is {tuple(prior_mean.shape)}, expected {(B, dout)}"
+        if prior_cov is not None:
+            prior_cov = dev32(prior_cov, ndim2=False)
+            if prior_cov.ndim == 2:
+                prior_cov = prior_cov[None]
+            assert prior_cov.shape == (B, dout, dout), f"before[1] is {tuple(prior_cov.shape)}, expected {(B, dout, dout)}"
+            prior_cov = prior_cov.contiguous()
+        else:
+            prior_logvar = dev32(prior_logvar)
+            assert prior_logvar.shape == (B, dout), f"the prior log-variance is {tuple(prior_logvar.shape)}, expected {(B, dout)}"
+        if observed is not None:
+            observed = torch.as_tensor(observed)
+            if observed.ndim == 1 and B == 1:
+                observed = observed[:, None]
+            assert observed.shape == (T, B), f"observed is {tuple(observed.shape)}, expected {(T, B)}"
+            observed = (observed != 0).to(device=y.device, dtype=torch.uint8).contiguous()
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        if d > dout and u is not None:
+            u = dev32(u, ndim2=False)
+            assert u.shape[0] == T, f"u has {u.shape[0]} rows, expected {T}"
+        u = self._tangent_u(u, T, B)
+        new = lambda *shape: torch.empty(*shape, device=y.device, dtype=torch.float32)       # noqa: E731
+        mean, var, loglik, cov_last = new(T, B, dout), new(T, B, dout), new(T, B), new(B, dout, dout)
+        cov = new(T, B, dout, dout) if return_cov else None
+        rc = N.lib().vjf_ekf(N.ptr(y), N.ptr(u), N.ptr(observed), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                             N.ptr(vel.w_mean), N.ptr(W), N.ptr(b), N.ptr(prior_mean), N.ptr(prior_logvar), N.ptr(prior_cov),
+                             N.ptr(mean), N.ptr(var), N.ptr(cov), N.ptr(loglik), N.ptr(cov_last), T, B, n, d, dout, dy,
+                             state_var, obs_var, stream_ptr())
+        if rc == -11:                             # the shape is beyond the plan (vjf_ekf_plan): nothing was launched
+            raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_ekf")
+        return EKFResult(mean, var, cov, loglik, (mean[-1], cov_last))
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1477,6 +1546,48 @@ class VJF(Module):
         """The smoothed posterior q(x_t | y_1..T) of a filtered sequence -- what `filter_sequence` / `fit` returned -- in one native
         call (RBFDS.smooth has the arguments); `model.decoder(res.gaussian().mean)` gives the smoothed observations."""
         return self.transition.smooth(q, u, state_var=state_var, after=after, return_cov=return_cov)
+
+    def ekf(self, y: Tensor, u: Tensor = None, *, x0: Gaussian = None, before: Tuple[Tensor, Tensor] = None, state_var: float = None,
+            obs_var: float = None, observed: Tensor = None, return_cov: bool = False) -> EKFResult:
+        """The extended Kalman filter of the learned generative model over a record as ONE C-ABI call (vjf_ekf; the contract is
+        stated in include/vjf_hip.h): the mean map and its Jacobian, the state noise, the linear decoder and the Gaussian
+        observation noise -- no recognition network.  It returns the filtered posterior with its full covariance and, row by row, the
+        model evidence log p(y_t | y_1..t-1), and it steps over rows that were not observed.
+        :param y: (T, B, ydim); (T, ydim) is one trial
+        :param u: (T, B, udim): u[t] drives the transition INTO row t, as in `filter`; row 0 is predicted from the prior with u[0]
+        :param x0: the prior of the row before row 0: None (the model's `prior`) or a Gaussian of (B, xdim)
+        :param before: (mean (B, xdim), cov (B, xdim, xdim)) in x0's place, such as a previous result's `head`: rows [0, k) first and
+            rows [k, T) with before = that head second give the bits of one call.  Giving both x0 and before is a ValueError
+        :param state_var: the scalar state-noise variance, default exp(transition.logvar);  obs_var: the scalar observation variance,
+            default exp(likelihood.logvar).  Reading a default copies one scalar to the host, which synchronises the stream; pass
+            floats to stay asynchronous
+        :param observed: (T, B) of booleans or 0 / 1, None: every row.  A row that is not observed is predicted only (its loglik is 0)
+            and its y is never used: it may hold NaN
+        :param return_cov: also return the full covariances of every row
+        :return: EKFResult(mean, var (T, B, xdim), cov (T, B, xdim, xdim) or None, loglik (T, B), head = (mean[-1], cov of the last
+            row)); `.gaussian()` is the diagonal posterior `smooth` takes (which then treats the filtered covariance as diagonal),
+            `.log_likelihood()` the evidence per trial.  A trial with a non-finite observed y, u or prior at some row, or a prior
+            covariance that is not positive definite, has NaN from that row on.
+        Under the Poisson likelihood this raises NotImplementedError: the update is the Gaussian one (a Laplace update is not
+        implemented).  Reads the model's state and writes none; no scratch."""
+        if isinstance(self.likelihood, PoissonLikelihood):
+            raise NotImplementedError("ekf needs the Gaussian likelihood: under the Poisson likelihood the update is not Gaussian "
+                                      "(a Laplace update is not implemented)")
+        if x0 is not None and before is not None:
+            raise ValueError("give x0 (a diagonal Gaussian) or before (mean, cov), not both")
+        y = dev32(y, ndim2=False)
+        B = 1 if y.ndim == 2 else y.shape[1]
+        p_mean = p_lv = p_cov = None
+        if before is not None:
+            p_mean, p_cov = before
+        elif x0 is not None:
+            p_mean, p_lv = x0.mean, x0.logvar
+        else:
+            one = torch.ones(B, self.xdim, device=self._blob.device)
+            p_mean, p_lv = one * torch.atleast_2d(self.mean), one * torch.atleast_2d(self.logvar)
+        state_var = float(self.transition.logvar.exp()) if state_var is None else float(state_var)
+        obs_var = float(self.likelihood.logvar.exp()) if obs_var is None else float(obs_var)
+        return self.transition._ekf(self.decoder, y, u, p_mean, p_lv, p_cov, state_var, obs_var, observed, return_cov)
 
     def sample_posterior(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, n_sample: int = 16, *,
                          state_var: float = None, noise: Tensor = None, after: Tensor = None) -> PosteriorSamples:
