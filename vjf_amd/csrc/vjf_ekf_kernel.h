@@ -29,11 +29,10 @@
 // trip count depends on data.  A trial with a non-finite m, u or observed y, or a pivot that is not positive and finite, has NaN written
 // over its carried moments and its log-likelihood: they stay NaN to the last row, and no other trial sees them.
 // Workgroups are independent: no cooperative launch, no hand-off, no scratch, no atomics.  Included by vjf_host_ekf.h.
-// `factor` is vjf_smooth_kernel.h's, statement for statement; that header stays as it is so that its kernels' assembly does not move
-// (profiles/ekf_isa.txt).  Whoever changes one changes both.
+// The factorisation, the staging of the prior's triangle and the rows written out are vjf_trial_algebra.h's, shared with vjf_smooth_kernel.h.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_flow_eval.h"           // flow_evaluate; the x step's FcTile, fc_stage, fc_u_ahead / fc_u_advance
+#include "vjf_trial_algebra.h"       // the lane view and helpers (ta_*); vjf_flow_eval.h: flow_evaluate, the x step's FcTile, fc_stage
 
 #define VJF_EKF_MAXDOUT 32           // dout <= 32: two indices per lane in the per-trial linear algebra, two output tiles of w_mean^T
 
@@ -65,10 +64,9 @@ __host__ __device__ static inline size_t vjf_ekf_ldt(int dout) { return dout <= 
 // (P and Ls; P^- and Lp; M and Lm), one pass's partial products (v of a round lies there too), Gc, the sixteen partial sums of
 // |y - b - C m|^2, the observed flags and (dec_lds) the decoder twice, (cen_lds) w_mean
 static inline size_t vjf_ekf_lds_floats(int n, int d, int dout, int dy, int vg, bool cen_lds, bool dec_lds) {
-    const size_t doutp = ((size_t)dout + 15) / 16 * 16, dyp = ((size_t)dy + 15) / 16 * 16, LD = VJF_LDT, tri = (size_t)dout * (dout + 1) / 2;
-    return vjf_fc_lds_floats(n, d, dout, cen_lds) + (size_t)n + 3 * (size_t)dout * LD + (size_t)dout * dout * LD + 3 * tri * LD +
-           (size_t)VJF_FC_WAVES * vg * doutp * LD + (size_t)dout * dout + 16 * LD + LD +
-           (dec_lds ? (size_t)dout * vjf_ekf_ldc(dy) + dyp * vjf_ekf_ldt(dout) : 0) + (cen_lds ? (size_t)n * dout : 0);
+    const size_t dyp = ((size_t)dy + 15) / 16 * 16, LD = VJF_LDT;
+    return vjf_trial_lds_floats(n, d, dout, vg, cen_lds, 3, 3) + (size_t)dout * dout + 16 * LD + LD +
+           (dec_lds ? (size_t)dout * vjf_ekf_ldc(dy) + dyp * vjf_ekf_ldt(dout) : 0);
 }
 
 // CL: centroids and w_mean in LDS (else read from global memory when they are used);  NO: output tiles of w_mean^T, dout <= 16 NO --
@@ -99,23 +97,15 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
     S.s_c = s_dect + (DL ? dyp * ldt : 0);        // n x d        centroids (CL): behind this kernel's buffers
     float* s_wm = S.s_c + n * d;                  // n x dout     w_mean (CL)
     float* s_v = s_ap;
-    const int tid = S.tid, lane = S.lane, wave = S.wave, b0 = S.b0, nb = S.nb, mi = S.mi, kk = S.kk, r4 = S.r4;
-    const size_t row0 = (size_t)b0 * dout, rowT = (size_t)B * dout;
+    const int tid = S.tid, wave = S.wave, b0 = S.b0, nb = S.nb, mi = S.mi, kk = S.kk, r4 = S.r4;
+    const size_t rowT = (size_t)B * dout;
     const float q = A.q, r = A.r, qnan = __builtin_nanf("");
     const float lconst = (float)dy * (1.8378770664093453f + logf(r));
-    auto tri = [](int i, int p) { return i * (i + 1) / 2 + p; };
 
     // ---- stage: widths, centroids, [prior mean, u_0], the prior's triangle, the flags of row 0, the decoder and Gc
     fc_stage<CL, true>(S, A.logw, A.c, s_iw2, A.prior_mean, nullptr, du > 0 ? A.u : nullptr);
     if (CL) for (int i = tid; i < n * dout; i += NTH) s_wm[i] = A.w[i];
-    for (int i = tid; i < TB * dout * dout; i += NTH) {
-        const int b = i / (dout * dout), rr = i - b * dout * dout, ii = rr / dout, j = rr - ii * dout;
-        if (j <= ii) {                            // rows beyond the batch carry the identity: finite, never stored
-            float v = ii == j ? 1.f : 0.f;
-            if (b < nb) v = A.prior_cov ? A.prior_cov[row0 * dout + i] : (ii == j ? expf(A.prior_lv[row0 + b * dout + ii]) : 0.f);
-            s_P[tri(ii, j) * LD + b] = v;
-        }
-    }
+    ta_stage_triangle(S, s_P, A.prior_cov, A.prior_lv);
     if (tid < TB) s_obs[tid] = tid < nb && (!A.obs || A.obs[b0 + tid]) ? 1.f : 0.f;
     if (DL)
         for (int e = tid; e < dyp * dout; e += NTH) {
@@ -150,44 +140,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
     __syncthreads();
 
     // the trial of this lane and its indices
-    const int b = wave * 4 + (lane >> 4), l16 = lane & 15;
-    auto sum16 = [](float s) {
-        s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
-        return s;
-    };
-    auto isfin = [](float v) { return fabsf(v) < INFINITY; };      // (a NaN compares false)
-    // the lower triangle at s_T becomes its Cholesky factor, a row per lane, column by column: what another lane needs of a row comes
-    // by a shuffle inside the sixteen.  True in every lane of the trial if every pivot is positive and finite.
-    auto factor = [&](float* s_T) {
-        bool ok = true;
-        for (int j = 0; j < dout; ++j) {
-            const int own = j & 15, ej = j >> 4;
-            const int rj = min(l16 + 16 * ej, dout - 1);              // the row of this lane that lane `own` has as row j
-            float a[2] = {0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < NO; ++e) {
-                const int i = l16 + 16 * e;
-                a[e] = (i >= j && i < dout) ? s_T[tri(i, j) * LD + b] : 0.f;
-            }
-            for (int p = 0; p < j; ++p) {
-                const float ljp = __shfl(s_T[tri(rj, min(p, rj)) * LD + b], own, 16);
-#pragma unroll
-                for (int e = 0; e < NO; ++e) {
-                    const int i = l16 + 16 * e;
-                    if (i >= j && i < dout) a[e] = fmaf(-s_T[tri(i, p) * LD + b], ljp, a[e]);
-                }
-            }
-            const float piv = __shfl(ej ? a[1] : a[0], own, 16);
-            ok = ok && piv > 0.f && piv < INFINITY;
-            const float dj = sqrtf(piv);
-#pragma unroll
-            for (int e = 0; e < NO; ++e) {
-                const int i = l16 + 16 * e;
-                if (i >= j && i < dout) s_T[tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
-            }
-        }
-        return ok;
-    };
+    const int b = ta_trial(S), l16 = ta_l16(S);
     // rows 16 yt .. 16 yt + 15 of C x for the tile's 16 trials, x at xs: K = dout in MFMA steps of 4, k ascending, the last step
     // padded with zeros.  Addresses beyond dy / dout are clamped and the value masked: nothing is read outside the arrays.
     auto decode = [&](const float* xs, int yt) {
@@ -203,21 +156,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
         return acc;
     };
     // this tile's rows of mean, var and (if asked for) cov of row t from the carried moments; cov_last at the last row.  All threads.
-    auto emit = [&](int t) {
-        for (int i = tid; i < nb * dout; i += NTH) {
-            const int bb = i / dout, j = i - bb * dout;
-            A.mean[(size_t)t * rowT + row0 + i] = s_x[j * LD + bb];
-            A.var[(size_t)t * rowT + row0 + i] = s_P[tri(j, j) * LD + bb];
-        }
-        float* full = A.cov ? A.cov + ((size_t)t * rowT + row0) * dout : nullptr;
-        if (full || t == T - 1)
-            for (int i = tid; i < nb * dout * dout; i += NTH) {
-                const int bb = i / (dout * dout), rr = i - bb * dout * dout, ii = rr / dout, j = rr - ii * dout;
-                const float v = s_P[tri(max(ii, j), min(ii, j)) * LD + bb];
-                if (full) full[i] = v;
-                if (t == T - 1) A.cov_last[row0 * dout + i] = v;
-            }
-    };
+    auto emit = [&](int t) { ta_emit_moments(S, s_x, s_P, t, rowT, A.mean, A.var, A.cov, t == T - 1, A.cov_last); };
 
     bool bad = false;
     for (int t = 0; t < T; ++t) {
@@ -241,14 +180,14 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
                 if (i < dout) {
                     const float xi = s_x[i * LD + b];
                     s_mp[i * LD + b] = xi + s_g[i * LD + b];
-                    nf += isfin(xi) ? 0.f : 1.f;
+                    nf += ta_isfin(xi) ? 0.f : 1.f;
                 }
             }
-            for (int j = dout + l16; j < d; j += 16) nf += isfin(s_x[j * LD + b]) ? 0.f : 1.f;
-            const float nfs = sum16(nf);          // (every lane of the wavefront takes part)
+            for (int j = dout + l16; j < d; j += 16) nf += ta_isfin(s_x[j * LD + b]) ? 0.f : 1.f;
+            const float nfs = ta_sum16(nf);          // (every lane of the wavefront takes part)
             bad = bad || nfs > 0.f;
         }
-        const bool okS = factor(s_P);
+        const bool okS = ta_factor<NO>(b, l16, dout, s_P);
         __syncthreads();
 
         // K = J Ls: row i of J; K[i][c] needs J[i][k] for k >= c only, so it takes A's place for c ascending
@@ -259,7 +198,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
                 float* ji = s_J + (size_t)i * LD + b;             // J[i][k] - delta_ik at ji[k * dout * LD]
                 for (int c = 0; c < dout; ++c) {
                     float k = 0.f;
-                    for (int p = c; p < dout; ++p) k = fmaf(ji[(size_t)p * dout * LD] + (p == i ? 1.f : 0.f), s_P[tri(p, c) * LD + b], k);
+                    for (int p = c; p < dout; ++p) k = fmaf(ji[(size_t)p * dout * LD] + (p == i ? 1.f : 0.f), s_P[ta_tri(p, c) * LD + b], k);
                     ji[(size_t)c * dout * LD] = k;
                 }
             }
@@ -276,11 +215,11 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
                     const float* kp = s_J + (size_t)p * LD + b;
                     float s = p == i ? q : 0.f;
                     for (int c = 0; c < dout; ++c) s = fmaf(ki[(size_t)c * dout * LD], kp[(size_t)c * dout * LD], s);
-                    s_Pp[tri(i, p) * LD + b] = s;
+                    s_Pp[ta_tri(i, p) * LD + b] = s;
                 }
             }
         }
-        const bool okP = factor(s_Pp);
+        const bool okP = ta_factor<NO>(b, l16, dout, s_Pp);
         __syncthreads();
 
         // W = Gc Lp: column p, in K's place; zero where the row is not observed
@@ -290,7 +229,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
             if (p < dout) {
                 for (int a = 0; a < dout; ++a) {
                     float s = 0.f;
-                    for (int c = dout - 1; c >= p; --c) s = fmaf(s_G[a * dout + c], s_Pp[tri(c, p) * LD + b], s);
+                    for (int c = dout - 1; c >= p; --c) s = fmaf(s_G[a * dout + c], s_Pp[ta_tri(c, p) * LD + b], s);
                     s_J[((size_t)a * dout + p) * LD + b] = obs ? s : 0.f;
                 }
             }
@@ -304,12 +243,12 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
             if (i < dout) {
                 for (int p = 0; p <= i; ++p) {
                     float s = p == i ? 1.f : 0.f;
-                    for (int a = dout - 1; a >= i; --a) s = fmaf(s_Pp[tri(a, i) * LD + b], s_J[((size_t)a * dout + p) * LD + b], s);
-                    s_M[tri(i, p) * LD + b] = s;
+                    for (int a = dout - 1; a >= i; --a) s = fmaf(s_Pp[ta_tri(a, i) * LD + b], s_J[((size_t)a * dout + p) * LD + b], s);
+                    s_M[ta_tri(i, p) * LD + b] = s;
                 }
             }
         }
-        const bool okM = factor(s_M);
+        const bool okM = ta_factor<NO>(b, l16, dout, s_M);
         __syncthreads();
 
         // Y = Lm^-1 Lp^T: column c by the forward solve, in W's place
@@ -319,9 +258,9 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
             if (c < dout) {
                 float* yc = s_J + (size_t)c * LD + b;             // Y[k][c] at yc[k * dout * LD]
                 for (int k = 0; k < dout; ++k) {
-                    float s = k <= c ? s_Pp[tri(c, min(k, c)) * LD + b] : 0.f;
-                    for (int p = 0; p < k; ++p) s = fmaf(-s_M[tri(k, p) * LD + b], yc[(size_t)p * dout * LD], s);
-                    yc[(size_t)k * dout * LD] = s / s_M[tri(k, k) * LD + b];
+                    float s = k <= c ? s_Pp[ta_tri(c, min(k, c)) * LD + b] : 0.f;
+                    for (int p = 0; p < k; ++p) s = fmaf(-s_M[ta_tri(k, p) * LD + b], yc[(size_t)p * dout * LD], s);
+                    yc[(size_t)k * dout * LD] = s / s_M[ta_tri(k, k) * LD + b];
                 }
             }
         }
@@ -337,7 +276,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
                     const float* yp = s_J + (size_t)p * LD + b;
                     float s = 0.f;
                     for (int k = 0; k < dout; ++k) s = fmaf(yi[(size_t)k * dout * LD], yp[(size_t)k * dout * LD], s);
-                    s_P[tri(i, p) * LD + b] = s;
+                    s_P[ta_tri(i, p) * LD + b] = s;
                 }
             }
         }
@@ -408,7 +347,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
             const int i = l16 + 16 * e;
             if (i < dout) {
                 float s = 0.f;
-                for (int p = 0; p < dout; ++p) s = fmaf(s_P[tri(max(i, p), min(i, p)) * LD + b], s_sv[p * LD + b], s);
+                for (int p = 0; p < dout; ++p) s = fmaf(s_P[ta_tri(max(i, p), min(i, p)) * LD + b], s_sv[p * LD + b], s);
                 const float mp = s_mp[i * LD + b];
                 s_x[i * LD + b] = obs ? mp + s : mp;
                 s_g[i * LD + b] = s;
@@ -446,23 +385,23 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_ekf_kernel(VjfEkfArgs A) {
             float q2 = 0.f, ld = 0.f, q1 = 0.f;
             for (int k = 0; k < dout; ++k) {
                 float s = s_g[k * LD + b];
-                for (int p = 0; p < k; ++p) s = fmaf(-s_Pp[tri(k, p) * LD + b], s_g[p * LD + b], s);
-                s /= s_Pp[tri(k, k) * LD + b];
+                for (int p = 0; p < k; ++p) s = fmaf(-s_Pp[ta_tri(k, p) * LD + b], s_g[p * LD + b], s);
+                s /= s_Pp[ta_tri(k, k) * LD + b];
                 s_g[k * LD + b] = s;
                 q2 = fmaf(s, s, q2);
-                ld += logf(s_M[tri(k, k) * LD + b]);
+                ld += logf(s_M[ta_tri(k, k) * LD + b]);
             }
             for (int p = 0; p < 16; ++p) q1 += s_q[p * LD + b];
             ll = -0.5f * (lconst + 2.f * ld + q1 / r + q2);
         }
         ll = __shfl(ll, 0, 16);
-        bad = bad || !okS || !okP || (obs && (!okM || !isfin(ll)));
+        bad = bad || !okS || !okP || (obs && (!okM || !ta_isfin(ll)));
 #pragma unroll
         for (int e = 0; e < NO; ++e) {
             const int i = l16 + 16 * e;
             if (i < dout && bad) {
                 s_x[i * LD + b] = qnan;
-                for (int p = 0; p <= i; ++p) s_P[tri(i, p) * LD + b] = qnan;
+                for (int p = 0; p <= i; ++p) s_P[ta_tri(i, p) * LD + b] = qnan;
             }
         }
         if (l16 == 0 && b < nb) A.ll[(size_t)t * B + b0 + b] = bad ? qnan : (obs ? ll : 0.f);

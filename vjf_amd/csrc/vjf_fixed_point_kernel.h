@@ -17,9 +17,9 @@
 // Workgroups are independent: no cooperative launch, no hand-off, no scratch, no atomics.  Included by vjf_host_fixed_point.h.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_forecast_kernel.h"     // vjf_rollout_step.h: the x step, FcTile, VJF_FC_THREADS / _WAVES, vjf_f32x4, VJF_LDT
+#include "vjf_trial_algebra.h"       // the lane view, ta_tri, ta_sum16; vjf_flow_eval.h: VJF_FLOW_MV, the x step's FcTile, fc_stage
 
-#define VJF_FP_MV 4                  // columns of A whose accumulators a wavefront holds while it walks its share of K
+#define VJF_FP_MV VJF_FLOW_MV       // columns of A whose accumulators a wavefront holds while it walks its share of K
 #define VJF_FP_MAXDOUT 32            // dout <= 32: two rows per lane in the per-trial linear algebra, two output tiles of w_mean^T
 
 namespace {
@@ -41,9 +41,7 @@ struct VjfFpArgs {
 // the x step's buffers plus 1 / width^2, the accepted x, g and b, A (the factor L takes its place between two evaluations), the lower
 // triangle of M, one pass's partial products and (cen_lds) w_mean
 static inline size_t vjf_fixed_point_lds_floats(int n, int d, int dout, int vg, bool cen_lds) {
-    const size_t doutp = ((size_t)dout + 15) / 16 * 16, LD = VJF_LDT, tri = (size_t)dout * (dout + 1) / 2;
-    return vjf_fc_lds_floats(n, d, dout, cen_lds) + (size_t)n + 3 * (size_t)dout * LD + (size_t)dout * dout * LD + tri * LD +
-           (size_t)VJF_FC_WAVES * vg * doutp * LD + (cen_lds ? (size_t)n * dout : 0);
+    return vjf_trial_lds_floats(n, d, dout, vg, cen_lds, 3, 1);
 }
 
 // CL: centroids and w_mean in LDS (else read from global memory when they are used);  NO: output tiles of w_mean^T, dout <= 16 NO --
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
     float* s_ap = s_M + ntri * LD;                // NW x vg x doutp x LD   the wavefronts' partial products of one pass
     const float* s_c = S.s_c = s_ap + NW * vg * doutp * LD;   // n x d   centroids (CL): behind this kernel's buffers
     float* s_wm = S.s_c + n * d;                  // n x dout     w_mean (CL)
-    const int tid = S.tid, lane = S.lane, wave = S.wave, b0 = S.b0, nb = S.nb, mi = S.mi, kk = S.kk, r4 = S.r4;
+    const int tid = S.tid, wave = S.wave, b0 = S.b0, nb = S.nb, mi = S.mi, kk = S.kk, r4 = S.r4;
     const size_t row0 = (size_t)b0 * dout;
 
     fc_stage<CL, true>(S, A.logw, A.c, s_iw2, A.x0, nullptr, A.u);
@@ -76,6 +74,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
     const float* W = CL ? s_wm : A.w;
 
     // g and A at the candidate in s_x: into s_g and s_A.  Barriers inside; s_x is complete before it and s_g, s_A behind it.
+    // (flow_evaluate's statements, kept here: with the call in their place this kernel runs 5 % longer, profiles/trial_algebra_ab.txt)
     auto evaluate = [&]() {
         fc_features<CL>(S, A.c);
         __syncthreads();
@@ -149,13 +148,8 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
     };
 
     // the trial of this lane and its rows
-    const int b = wave * 4 + (lane >> 4), l16 = lane & 15;
+    const int b = ta_trial(S), l16 = ta_l16(S);
     const bool bv = b < nb;
-    auto sum16 = [](float s) {
-        s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
-        return s;
-    };
-    auto tri = [](int i, int p) { return i * (i + 1) / 2 + p; };
     const float tol2 = A.tol * A.tol;
     float r2 = INFINITY, lam = A.lam0;            // (the same in the sixteen lanes of a trial)
     bool done = !bv;                              // rows beyond the batch hold zeros and are never touched
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
                             const float* ap = s_A + (size_t)p * dout * LD + b;
                             float m = 0.f;
                             for (int i = 0; i < dout; ++i) m = fmaf(aj[i * LD], ap[i * LD], m);
-                            s_M[tri(j, p) * LD + b] = m;
+                            s_M[ta_tri(j, p) * LD + b] = m;
                         }
                     }
                 }
@@ -204,9 +198,10 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
 #pragma unroll
             for (int e = 0; e < NO; ++e) {
                 const int i = l16 + 16 * e;
-                if (i < dout) dg += s_M[tri(i, i) * LD + b];
+                if (i < dout) dg += s_M[ta_tri(i, i) * LD + b];
             }
-            const float shift = lam * (sum16(dg) / (float)dout);
+            const float shift = lam * (ta_sum16(dg) / (float)dout);
+            // (ta_factor's statements with M + shift I read from s_M, kept here: shared, this kernel ran 0.8 % longer, profiles/trial_algebra_ab.txt)
             bool ok = true;
             for (int j = 0; j < dout; ++j) {
                 const int own = j & 15, ej = j >> 4;
@@ -215,14 +210,14 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
 #pragma unroll
                 for (int e = 0; e < NO; ++e) {
                     const int i = l16 + 16 * e;
-                    a[e] = (i >= j && i < dout) ? s_M[tri(i, j) * LD + b] + (i == j ? shift : 0.f) : 0.f;
+                    a[e] = (i >= j && i < dout) ? s_M[ta_tri(i, j) * LD + b] + (i == j ? shift : 0.f) : 0.f;
                 }
                 for (int p = 0; p < j; ++p) {
-                    const float ljp = __shfl(s_L[tri(rj, min(p, rj)) * LD + b], own, 16);
+                    const float ljp = __shfl(s_L[ta_tri(rj, min(p, rj)) * LD + b], own, 16);
 #pragma unroll
                     for (int e = 0; e < NO; ++e) {
                         const int i = l16 + 16 * e;
-                        if (i >= j && i < dout) a[e] = fmaf(-s_L[tri(i, p) * LD + b], ljp, a[e]);
+                        if (i >= j && i < dout) a[e] = fmaf(-s_L[ta_tri(i, p) * LD + b], ljp, a[e]);
                     }
                 }
                 const float piv = __shfl(ej ? a[1] : a[0], own, 16);
@@ -231,7 +226,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
 #pragma unroll
                 for (int e = 0; e < NO; ++e) {
                     const int i = l16 + 16 * e;
-                    if (i >= j && i < dout) s_L[tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
+                    if (i >= j && i < dout) s_L[ta_tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
                 }
             }
             // L y = -b, column by column: y_j is final once the columns before it are taken off
@@ -244,12 +239,12 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
             for (int j = 0; j < dout; ++j) {
                 const int own = j & 15, ej = j >> 4;
                 const int rj = min(l16 + 16 * ej, dout - 1);
-                const float yj = __shfl((ej ? t[1] : t[0]) / s_L[tri(rj, min(j, rj)) * LD + b], own, 16);
+                const float yj = __shfl((ej ? t[1] : t[0]) / s_L[ta_tri(rj, min(j, rj)) * LD + b], own, 16);
 #pragma unroll
                 for (int e = 0; e < NO; ++e) {
                     const int i = l16 + 16 * e;
                     if (i == j) t[e] = yj;
-                    else if (i > j && i < dout) t[e] = fmaf(-s_L[tri(i, j) * LD + b], yj, t[e]);
+                    else if (i > j && i < dout) t[e] = fmaf(-s_L[ta_tri(i, j) * LD + b], yj, t[e]);
                 }
             }
             // L^T delta = y, from the last row up: row j of L^T is column j of L, a row per lane, summed over the sixteen lanes
@@ -258,12 +253,12 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_fixed_point_kernel(VjfFpAr
 #pragma unroll
                 for (int e = 0; e < NO; ++e) {
                     const int i = l16 + 16 * e;
-                    if (i > j && i < dout) s = fmaf(s_L[tri(i, j) * LD + b], t[e], s);
+                    if (i > j && i < dout) s = fmaf(s_L[ta_tri(i, j) * LD + b], t[e], s);
                 }
-                s = sum16(s);
+                s = ta_sum16(s);
 #pragma unroll
                 for (int e = 0; e < NO; ++e)
-                    if (l16 + 16 * e == j) t[e] = (t[e] - s) / s_L[tri(j, j) * LD + b];
+                    if (l16 + 16 * e == j) t[e] = (t[e] - s) / s_L[ta_tri(j, j) * LD + b];
             }
             if (act) {
 #pragma unroll

@@ -9,8 +9,8 @@
 //
 // This is vjf_fixed_point_kernel's `evaluate`, statement for statement.  That kernel keeps its own copy as a lambda: with the lambda
 // replaced by a call of this function its assembly moves (profiles/smoother_isa.txt: <1,1> 92 -> 96 and <0,1> 91 -> 97 VGPRs, the
-// other two forms shorter but different), so it is left as it was measured; vjf_smooth_kernel.h calls this one.  Whoever changes one
-// changes both.  profiles/mega_split_isa.txt is the precedent for such a duplicate.
+// other two forms shorter but different) and it runs 5 % longer (profiles/trial_algebra_ab.txt); the smoother, the sampler and the
+// EKF call this one.  Whoever changes one changes both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vjf_forecast_kernel.h"     // vjf_rollout_step.h: the x step, FcTile, VJF_FC_THREADS / _WAVES, vjf_f32x4, VJF_LDT

@@ -3,6 +3,7 @@
 // Included by vjf_abi.hip only, behind vjf_host_ctx.h (fail, allow_lds, kMaxLds) and vjf_host_forecast.h (fc_env_on).
 #pragma once
 #include "vjf_ekf_kernel.h"        // vjf_ekf_kernel
+#include "vjf_host_tile_forms.h"    // tile_plan_cl_vg, with_tile_form, with_flag, launch_tile_form
 
 namespace {
 
@@ -17,17 +18,13 @@ namespace {
 //      fits == false: the entry point refuses (dout beyond VJF_EKF_MAXDOUT, or not one pass fits).
 struct EkfPlan { bool fits, cl, dl; int vg; size_t lds; };
 EkfPlan ekf_plan(int n, int d, int dout, int dy, bool cen_lds, bool dec_lds) {
-    const size_t budget = kMaxLds - 1024;
     EkfPlan p{};
     if (dout > VJF_EKF_MAXDOUT) return p;
-    p.cl = cen_lds && vjf_ekf_lds_floats(n, d, dout, dy, dout < VJF_FLOW_MV ? dout : VJF_FLOW_MV, true, false) * 4 <= budget;
-    int vg = dout;
-    while (vg >= 1 && vjf_ekf_lds_floats(n, d, dout, dy, vg, p.cl, false) * 4 > budget) --vg;
-    if (vg < 1) return p;
-    p.fits = true;
-    p.vg = vg;
-    p.dl = dec_lds && vjf_ekf_lds_floats(n, d, dout, dy, vg, p.cl, true) * 4 <= budget;
-    p.lds = vjf_ekf_lds_floats(n, d, dout, dy, vg, p.cl, p.dl) * 4;
+    auto bytes = [&](int vg, bool cl, bool dl) { return vjf_ekf_lds_floats(n, d, dout, dy, vg, cl, dl) * 4; };
+    p.fits = tile_plan_cl_vg(dout, cen_lds, [&](int vg, bool cl) { return bytes(vg, cl, false); }, p.cl, p.vg);
+    if (!p.fits) return p;
+    p.dl = dec_lds && bytes(p.vg, p.cl, true) <= kTileLdsBudget;
+    p.lds = bytes(p.vg, p.cl, p.dl);
     return p;
 }
 
@@ -35,21 +32,11 @@ EkfPlan ekf_plan(int n, int d, int dout, int dy, bool cen_lds, bool dec_lds) {
 int ekf_run(VjfEkfArgs a, const EkfPlan& p, hipStream_t s) {
     const int tiles = (a.B + 15) / 16;
     a.vg = p.vg;
-    auto launch = [&](auto cl, auto no, auto dl) {
-        auto kernel = vjf_ekf_kernel<decltype(cl)::value, decltype(no)::value, decltype(dl)::value>;
-        allow_lds(kernel, p.lds);
-        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(VJF_FC_THREADS), p.lds, s, a);
-    };
-    auto with_dl = [&](auto cl, auto no) {
-        if (p.dl) launch(cl, no, std::true_type{});
-        else launch(cl, no, std::false_type{});
-    };
-    auto with_no = [&](auto cl) {
-        if (a.dout <= 16) with_dl(cl, std::integral_constant<int, 1>{});
-        else with_dl(cl, std::integral_constant<int, 2>{});
-    };
-    if (p.cl) with_no(std::true_type{});
-    else with_no(std::false_type{});
+    with_tile_form(p.cl, a.dout, [&](auto cl, auto no) {
+        with_flag(p.dl, [&](auto dl) {
+            launch_tile_form(vjf_ekf_kernel<decltype(cl)::value, decltype(no)::value, decltype(dl)::value>, dim3(tiles), p.lds, s, a);
+        });
+    });
     VJF_HIP(hipGetLastError());
     return 0;
 }

@@ -3,6 +3,7 @@
 // Included by vjf_abi.hip only, behind vjf_host_ctx.h (fail, allow_lds, kMaxLds) and vjf_host_forecast.h (fc_env_on).
 #pragma once
 #include "vjf_smooth_kernel.h"     // vjf_smooth_kernel
+#include "vjf_host_tile_forms.h"    // tile_plan_cl_vg, with_tile_form, launch_tile_form
 
 namespace {
 
@@ -28,16 +29,12 @@ __device__ __attribute__((used)) const unsigned char vjf_text_pad[4544] = {1};
 //      refuses (dout beyond VJF_SM_MAXDOUT, or not one pass fits).
 struct SmPlan { bool fits, cl; int vg; size_t lds; };
 SmPlan sm_plan(int n, int d, int dout, bool cen_lds) {
-    const size_t budget = kMaxLds - 1024;
     SmPlan p{};
     if (dout > VJF_SM_MAXDOUT) return p;
-    p.cl = cen_lds && vjf_smooth_lds_floats(n, d, dout, dout < VJF_FLOW_MV ? dout : VJF_FLOW_MV, true) * 4 <= budget;
-    int vg = dout;
-    while (vg >= 1 && vjf_smooth_lds_floats(n, d, dout, vg, p.cl) * 4 > budget) --vg;
-    if (vg < 1) return p;
-    p.fits = true;
-    p.vg = vg;
-    p.lds = vjf_smooth_lds_floats(n, d, dout, vg, p.cl) * 4;
+    auto bytes = [&](int vg, bool cl) { return vjf_smooth_lds_floats(n, d, dout, vg, cl) * 4; };
+    p.fits = tile_plan_cl_vg(dout, cen_lds, bytes, p.cl, p.vg);
+    if (!p.fits) return p;
+    p.lds = bytes(p.vg, p.cl);
     return p;
 }
 
@@ -45,17 +42,9 @@ SmPlan sm_plan(int n, int d, int dout, bool cen_lds) {
 int smooth_run(VjfSmArgs a, const SmPlan& p, hipStream_t s) {
     const int tiles = (a.B + 15) / 16;
     a.vg = p.vg;
-    auto launch = [&](auto cl, auto no) {
-        auto kernel = vjf_smooth_kernel<decltype(cl)::value, decltype(no)::value>;
-        allow_lds(kernel, p.lds);
-        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(VJF_FC_THREADS), p.lds, s, a);
-    };
-    auto with_no = [&](auto cl) {
-        if (a.dout <= 16) launch(cl, std::integral_constant<int, 1>{});
-        else launch(cl, std::integral_constant<int, 2>{});
-    };
-    if (p.cl) with_no(std::true_type{});
-    else with_no(std::false_type{});
+    with_tile_form(p.cl, a.dout, [&](auto cl, auto no) {
+        launch_tile_form(vjf_smooth_kernel<decltype(cl)::value, decltype(no)::value>, dim3(tiles), p.lds, s, a);
+    });
     VJF_HIP(hipGetLastError());
     return 0;
 }

@@ -4,6 +4,7 @@
 // vjf_host_smooth.h (sm_plan).
 #pragma once
 #include "vjf_smooth_sample_kernel.h"     // vjf_smooth_sample_kernel
+#include "vjf_host_tile_forms.h"           // kTileLdsBudget, with_tile_form, launch_tile_form
 
 namespace {
 
@@ -21,7 +22,7 @@ namespace {
 //      entry point refuses.
 struct SmsPlan { bool fits, cl; int vg, sc; size_t lds; };
 SmsPlan sms_plan(int n, int d, int dout, int S, bool cen_lds, int members = 0) {
-    const size_t budget = kMaxLds - 1024;
+    const size_t budget = kTileLdsBudget;
     SmsPlan p{};
     if (dout > VJF_SMS_MAXDOUT || S < 1 || !sm_plan(n, d, dout, cen_lds).fits) return p;
     auto bytes = [&](int vg, int sc, bool cl) { return vjf_sms_lds_floats(n, d, dout, vg, sc, cl) * 4; };
@@ -46,17 +47,9 @@ int smooth_sample_run(VjfSmsArgs a, const SmsPlan& p, hipStream_t s) {
     const int tiles = (a.B + 15) / 16, chunks = (a.S + p.sc - 1) / p.sc;
     a.vg = p.vg;
     a.sc = p.sc;
-    auto launch = [&](auto cl, auto no) {
-        auto kernel = vjf_smooth_sample_kernel<decltype(cl)::value, decltype(no)::value>;
-        allow_lds(kernel, p.lds);
-        hipLaunchKernelGGL(kernel, dim3(tiles, chunks), dim3(VJF_FC_THREADS), p.lds, s, a);
-    };
-    auto with_no = [&](auto cl) {
-        if (a.dout <= 16) launch(cl, std::integral_constant<int, 1>{});
-        else launch(cl, std::integral_constant<int, 2>{});
-    };
-    if (p.cl) with_no(std::true_type{});
-    else with_no(std::false_type{});
+    with_tile_form(p.cl, a.dout, [&](auto cl, auto no) {
+        launch_tile_form(vjf_smooth_sample_kernel<decltype(cl)::value, decltype(no)::value>, dim3(tiles, chunks), p.lds, s, a);
+    });
     VJF_HIP(hipGetLastError());
     return 0;
 }

@@ -19,11 +19,12 @@
 // depends on data.  A trial whose inputs are not finite, or whose factor has a pivot that is not positive and finite, has NaN written
 // over its carried moments: they stay NaN down to row 0, and no other trial sees them.
 // Workgroups are independent: no cooperative launch, no hand-off, no scratch, no atomics.  Included by vjf_host_smooth.h.
-// vjf_smooth_sample_kernel.h has its own copy of `factor` and of the scale, factor and gain phases, statement for statement; these
-// stay where they are so that this kernel's assembly does not move (profiles/sampler_isa.txt).  Whoever changes one changes both.
+// The factorisation, the staging of the carried triangle and the rows written out are vjf_trial_algebra.h's, shared with
+// vjf_ekf_kernel.h.  vjf_smooth_sample_kernel.h has its own copy of the factorisation and of the scale, factor and gain phases,
+// statement for statement: with either shared its kernel ran 2 % longer (profiles/trial_algebra_ab.txt).  Whoever changes one changes both.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_flow_eval.h"           // flow_evaluate; the x step's FcTile, fc_stage, fc_u_ahead / fc_u_advance
+#include "vjf_trial_algebra.h"       // the lane view and helpers (ta_*); vjf_flow_eval.h: flow_evaluate, the x step's FcTile, fc_stage
 
 #define VJF_SM_MAXDOUT 32            // dout <= 32: two indices per lane in the per-trial linear algebra, two output tiles of w_mean^T
 
@@ -46,9 +47,7 @@ struct VjfSmArgs {
 // the x step's buffers plus 1 / width^2, four vectors (g, ms, sd, dl), the block (A, Jh, G, K in turn), the two triangles (M and L; Ps
 // and Ls), one pass's partial products and (cen_lds) w_mean
 static inline size_t vjf_smooth_lds_floats(int n, int d, int dout, int vg, bool cen_lds) {
-    const size_t doutp = ((size_t)dout + 15) / 16 * 16, LD = VJF_LDT, tri = (size_t)dout * (dout + 1) / 2;
-    return vjf_fc_lds_floats(n, d, dout, cen_lds) + (size_t)n + 4 * (size_t)dout * LD + (size_t)dout * dout * LD + 2 * tri * LD +
-           (size_t)VJF_FC_WAVES * vg * doutp * LD + (cen_lds ? (size_t)n * dout : 0);
+    return vjf_trial_lds_floats(n, d, dout, vg, cen_lds, 4, 2);
 }
 
 // CL: centroids and w_mean in LDS (else read from global memory when they are used);  NO: output tiles of w_mean^T, dout <= 16 NO --
@@ -71,12 +70,11 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
     float* s_ap = s_P + ntri * LD;                // NW x vg x doutp x LD   the wavefronts' partial products of one pass
     S.s_c = s_ap + NW * A.vg * doutp * LD;        // n x d        centroids (CL): behind this kernel's buffers
     float* s_wm = S.s_c + n * d;                  // n x dout     w_mean (CL)
-    const int tid = S.tid, lane = S.lane, wave = S.wave, b0 = S.b0, nb = S.nb;
+    const int tid = S.tid, b0 = S.b0, nb = S.nb;
     const size_t row0 = (size_t)b0 * dout, rowT = (size_t)B * dout;
     const bool after = A.after_mean != nullptr;
     const int ts = after ? T - 1 : T - 2;         // the first row that is smoothed by a step; the row behind it is the carried one
     const float rsq = A.rsq, qnan = __builtin_nanf("");
-    auto tri = [](int i, int p) { return i * (i + 1) / 2 + p; };
 
     // ---- stage: widths, centroids, [mu_ts, u_{ts+1}], sd of row ts, and the carried moments
     {
@@ -90,74 +88,16 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
             s_sd[j * LD + b] = live ? expf(0.5f * A.lv[(size_t)t0 * rowT + row0 + i]) : 1.f;
             s_ms[j * LD + b] = live ? (after ? A.after_mean[row0 + i] : A.mu[(size_t)(T - 1) * rowT + row0 + i]) : 0.f;
         }
-        for (int i = tid; i < TB * dout * dout; i += NTH) {
-            const int b = i / (dout * dout), r = i - b * dout * dout, ii = r / dout, j = r - ii * dout;
-            if (j <= ii) {                        // rows beyond the batch carry the identity: finite, never stored
-                float v = ii == j ? 1.f : 0.f;
-                if (b < nb) v = after ? A.after_cov[row0 * dout + i] : (ii == j ? expf(A.lv[(size_t)(T - 1) * rowT + row0 + b * dout + ii]) : 0.f);
-                s_P[tri(ii, j) * LD + b] = v;
-            }
-        }
+        ta_stage_triangle(S, s_P, after ? A.after_cov : nullptr, A.lv + (size_t)(T - 1) * rowT);
     }
     FlowEval E;
     E.W = CL ? s_wm : A.w; E.c = A.c; E.s_iw2 = s_iw2; E.s_g = s_g; E.s_A = s_J; E.s_ap = s_ap; E.vg = A.vg;
     __syncthreads();
 
     // the trial of this lane and its indices
-    const int b = wave * 4 + (lane >> 4), l16 = lane & 15;
-    auto sum16 = [](float s) {
-        s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
-        return s;
-    };
-    auto isfin = [](float v) { return fabsf(v) < INFINITY; };      // (a NaN compares false)
-    // the lower triangle at s_T becomes its Cholesky factor, a row per lane, column by column: what another lane needs of a row comes
-    // by a shuffle inside the sixteen.  True in every lane of the trial if every pivot is positive and finite.
-    auto factor = [&](float* s_T) {
-        bool ok = true;
-        for (int j = 0; j < dout; ++j) {
-            const int own = j & 15, ej = j >> 4;
-            const int rj = min(l16 + 16 * ej, dout - 1);              // the row of this lane that lane `own` has as row j
-            float a[2] = {0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < NO; ++e) {
-                const int i = l16 + 16 * e;
-                a[e] = (i >= j && i < dout) ? s_T[tri(i, j) * LD + b] : 0.f;
-            }
-            for (int p = 0; p < j; ++p) {
-                const float ljp = __shfl(s_T[tri(rj, min(p, rj)) * LD + b], own, 16);
-#pragma unroll
-                for (int e = 0; e < NO; ++e) {
-                    const int i = l16 + 16 * e;
-                    if (i >= j && i < dout) a[e] = fmaf(-s_T[tri(i, p) * LD + b], ljp, a[e]);
-                }
-            }
-            const float piv = __shfl(ej ? a[1] : a[0], own, 16);
-            ok = ok && piv > 0.f && piv < INFINITY;
-            const float dj = sqrtf(piv);
-#pragma unroll
-            for (int e = 0; e < NO; ++e) {
-                const int i = l16 + 16 * e;
-                if (i >= j && i < dout) s_T[tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
-            }
-        }
-        return ok;
-    };
+    const int b = ta_trial(S), l16 = ta_l16(S);
     // this tile's rows of mean, var and (if asked for) cov of row t from the carried moments; cov0 at row 0.  All threads; no barrier.
-    auto emit = [&](int t) {
-        for (int i = tid; i < nb * dout; i += NTH) {
-            const int bb = i / dout, j = i - bb * dout;
-            A.mean[(size_t)t * rowT + row0 + i] = s_ms[j * LD + bb];
-            A.var[(size_t)t * rowT + row0 + i] = s_P[tri(j, j) * LD + bb];
-        }
-        float* full = A.cov ? A.cov + ((size_t)t * rowT + row0) * dout : nullptr;
-        if (full || t == 0)
-            for (int i = tid; i < nb * dout * dout; i += NTH) {
-                const int bb = i / (dout * dout), r = i - bb * dout * dout, ii = r / dout, j = r - ii * dout;
-                const float v = s_P[tri(max(ii, j), min(ii, j)) * LD + bb];
-                if (full) full[i] = v;
-                if (t == 0) A.cov0[row0 * dout + i] = v;
-            }
-    };
+    auto emit = [&](int t) { ta_emit_moments(S, s_ms, s_P, t, rowT, A.mean, A.var, A.cov, t == 0, A.cov0); };
 
     // ---- the carried row: a moment that is not finite, or (the last row of the record) a variance that is not positive, poisons the trial
     bool bad;
@@ -167,18 +107,18 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
         for (int e = 0; e < NO; ++e) {
             const int j = l16 + 16 * e;
             if (j < dout) {
-                const float pj = s_P[tri(j, j) * LD + b];
-                nf += isfin(s_ms[j * LD + b]) && (after || (pj > 0.f && pj < INFINITY)) ? 0.f : 1.f;
+                const float pj = s_P[ta_tri(j, j) * LD + b];
+                nf += ta_isfin(s_ms[j * LD + b]) && (after || (pj > 0.f && pj < INFINITY)) ? 0.f : 1.f;
             }
         }
-        const float nfs = sum16(nf);
+        const float nfs = ta_sum16(nf);
         bad = nfs > 0.f;
 #pragma unroll
         for (int e = 0; e < NO; ++e) {
             const int j = l16 + 16 * e;
             if (j < dout && bad) {
                 s_ms[j * LD + b] = qnan;
-                for (int p = 0; p <= j; ++p) s_P[tri(j, p) * LD + b] = qnan;
+                for (int p = 0; p <= j; ++p) s_P[ta_tri(j, p) * LD + b] = qnan;
             }
         }
     }
@@ -211,11 +151,11 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
                     float* aj = s_J + (size_t)j * dout * LD + b;
                     for (int i = 0; i < dout; ++i) aj[i * LD] = (aj[i * LD] + (i == j ? 1.f : 0.f)) * sc;
                     s_dl[j * LD + b] = s_ms[j * LD + b] - (xj + s_g[j * LD + b]);
-                    nf += isfin(xj) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
+                    nf += ta_isfin(xj) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
                 }
             }
-            for (int j = dout + l16; j < d; j += 16) nf += isfin(s_x[j * LD + b]) ? 0.f : 1.f;
-            const float nfs = sum16(nf);          // (every lane of the wavefront takes part)
+            for (int j = dout + l16; j < d; j += 16) nf += ta_isfin(s_x[j * LD + b]) ? 0.f : 1.f;
+            const float nfs = ta_sum16(nf);          // (every lane of the wavefront takes part)
             bad = bad || nfs > 0.f;
         }
         __syncthreads();
@@ -230,12 +170,12 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
                     const float* ap = s_J + (size_t)p * dout * LD + b;
                     float m = p == j ? 1.f : 0.f;
                     for (int i = 0; i < dout; ++i) m = fmaf(aj[i * LD], ap[i * LD], m);
-                    s_L[tri(j, p) * LD + b] = m;
+                    s_L[ta_tri(j, p) * LD + b] = m;
                 }
             }
         }
-        const bool okL = factor(s_L);
-        const bool okP = factor(s_P);
+        const bool okL = ta_factor<NO>(b, l16, dout, s_L);
+        const bool okP = ta_factor<NO>(b, l16, dout, s_P);
         bad = bad || !okL || !okP;
         __syncthreads();
 
@@ -247,13 +187,13 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
                 float* yi = s_J + (size_t)i * LD + b;             // element j at yi[j * dout * LD]
                 for (int j = 0; j < dout; ++j) {
                     float s = yi[(size_t)j * dout * LD];
-                    for (int p = 0; p < j; ++p) s = fmaf(-s_L[tri(j, p) * LD + b], yi[(size_t)p * dout * LD], s);
-                    yi[(size_t)j * dout * LD] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = 0; p < j; ++p) s = fmaf(-s_L[ta_tri(j, p) * LD + b], yi[(size_t)p * dout * LD], s);
+                    yi[(size_t)j * dout * LD] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int j = dout - 1; j >= 0; --j) {
                     float s = yi[(size_t)j * dout * LD];
-                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[tri(p, j) * LD + b], yi[(size_t)p * dout * LD], s);
-                    yi[(size_t)j * dout * LD] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[ta_tri(p, j) * LD + b], yi[(size_t)p * dout * LD], s);
+                    yi[(size_t)j * dout * LD] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int j = 0; j < dout; ++j) yi[(size_t)j * dout * LD] *= s_sd[j * LD + b] * rsq;
             }
@@ -271,7 +211,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
                 s_ms[j * LD + b] = bad ? qnan : s_x[j * LD + b] + m;
                 for (int c = 0; c < dout; ++c) {
                     float k = 0.f;
-                    for (int i = c; i < dout; ++i) k = fmaf(gj[i * LD], s_P[tri(i, c) * LD + b], k);
+                    for (int i = c; i < dout; ++i) k = fmaf(gj[i * LD], s_P[ta_tri(i, c) * LD + b], k);
                     gj[c * LD] = k;
                 }
             }
@@ -285,13 +225,13 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
             if (i < dout) {
                 for (int j = i; j < dout; ++j) {
                     float s = j == i ? 1.f : 0.f;
-                    for (int p = i; p < j; ++p) s = fmaf(-s_L[tri(j, p) * LD + b], s_P[tri(p, i) * LD + b], s);
-                    s_P[tri(j, i) * LD + b] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = i; p < j; ++p) s = fmaf(-s_L[ta_tri(j, p) * LD + b], s_P[ta_tri(p, i) * LD + b], s);
+                    s_P[ta_tri(j, i) * LD + b] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int j = dout - 1; j >= i; --j) {
-                    float s = s_P[tri(j, i) * LD + b];
-                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[tri(p, j) * LD + b], s_P[tri(p, i) * LD + b], s);
-                    s_P[tri(j, i) * LD + b] = s / s_L[tri(j, j) * LD + b];
+                    float s = s_P[ta_tri(j, i) * LD + b];
+                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[ta_tri(p, j) * LD + b], s_P[ta_tri(p, i) * LD + b], s);
+                    s_P[ta_tri(j, i) * LD + b] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 const float* ki = s_J + (size_t)i * dout * LD + b;
                 const float sdi = s_sd[i * LD + b];
@@ -299,7 +239,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_kernel(VjfSmArgs A)
                     const float* kj = s_J + (size_t)j * dout * LD + b;
                     float kk = 0.f;
                     for (int c = 0; c < dout; ++c) kk = fmaf(kj[c * LD], ki[c * LD], kk);
-                    s_P[tri(j, i) * LD + b] = bad ? qnan : fmaf(s_sd[j * LD + b] * sdi, s_P[tri(j, i) * LD + b], kk);
+                    s_P[ta_tri(j, i) * LD + b] = bad ? qnan : fmaf(s_sd[j * LD + b] * sdi, s_P[ta_tri(j, i) * LD + b], kk);
                 }
             }
         }

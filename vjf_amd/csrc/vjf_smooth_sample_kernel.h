@@ -14,8 +14,9 @@
 //       members   lane l of the trial takes members l, l + 16, .. of the chunk, one after the other: the back-substitution
 //                 L^T w = z in the noise's place, dl = x_{t+1} - (mu_t + g) in the draw's place, then row by row
 //                 x_t[j] = (mu_t[j] + G[j][:] dl) + sd_j w_j in the noise's place; the two buffers then change roles
-//     a barrier between the phases.  scale, factor and gain are vjf_smooth_kernel's statements (that kernel keeps its own: its
-//     assembly is a yardstick of profiles/sampler_isa.txt and was left untouched; whoever changes one changes both).  The mean sum
+//     a barrier between the phases.  scale, factor and gain are vjf_smooth_kernel's statements and `factor` is
+//     vjf_trial_algebra.h's ta_factor, kept here as copies: with either shared this kernel ran 2 % longer
+//     (profiles/trial_algebra_ab.txt); whoever changes one changes both.  The mean sum
 //     keeps the smoother's order and the noise term is added last, so zero noise returns the smoother's mean bit for bit.
 // Member m of the chunk lies at m * MS + j * 18 + trial with MS = 2 ((9 dout) | 1) floats: in the members phase the sixteen lanes
 // of a trial then touch sixteen distinct even banks (mod 32: MS / 2 is odd) and the other trial of the half-wave the odd ones, so
@@ -28,7 +29,7 @@
 // Workgroups are independent: no cooperative launch, no hand-off, no scratch, no atomics.  Included by vjf_host_smooth_sample.h.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "vjf_flow_eval.h"           // flow_evaluate; the x step's FcTile, fc_stage, fc_u_ahead / fc_u_advance
+#include "vjf_trial_algebra.h"       // the lane view and helpers (ta_*); vjf_flow_eval.h: flow_evaluate, the x step's FcTile, fc_stage
 
 #define VJF_SMS_MAXDOUT 32           // as VJF_SM_MAXDOUT: two indices per lane, two output tiles of w_mean^T
 #define VJF_SMS_LDM 18               // floats between two elements of a member (16 trials and two of padding: see above)
@@ -55,9 +56,7 @@ static inline size_t vjf_sms_member_floats(int dout) { return 2 * (size_t)((9 * 
 // the x step's buffers plus 1 / width^2, two vectors (g, sd), the block (A, Jh, G in turn), one triangle (M, L), one pass's partial
 // products, the two member buffers (draws and noise) and (cen_lds) w_mean
 static inline size_t vjf_sms_lds_floats(int n, int d, int dout, int vg, int sc, bool cen_lds) {
-    const size_t doutp = ((size_t)dout + 15) / 16 * 16, LD = VJF_LDT, tri = (size_t)dout * (dout + 1) / 2;
-    return vjf_fc_lds_floats(n, d, dout, cen_lds) + (size_t)n + 2 * (size_t)dout * LD + (size_t)dout * dout * LD + tri * LD +
-           (size_t)VJF_FC_WAVES * vg * doutp * LD + 2 * (size_t)sc * vjf_sms_member_floats(dout) + (cen_lds ? (size_t)n * dout : 0);
+    return vjf_trial_lds_floats(n, d, dout, vg, cen_lds, 2, 1) + 2 * (size_t)sc * vjf_sms_member_floats(dout);
 }
 
 // CL: centroids and w_mean in LDS (else read from global memory when they are used);  NO: output tiles of w_mean^T, dout <= 16 NO --
@@ -80,14 +79,13 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
     float* zc = xc + A.sc * MS;                   // sc x MS      the members' noise of row t; the draws of row t behind the members phase
     S.s_c = zc + A.sc * MS;                       // n x d        centroids (CL): behind this kernel's buffers
     float* s_wm = S.s_c + n * d;                  // n x dout     w_mean (CL)
-    const int tid = S.tid, lane = S.lane, wave = S.wave, b0 = S.b0, nb = S.nb;
+    const int tid = S.tid, b0 = S.b0, nb = S.nb;
     const size_t row0 = (size_t)b0 * dout, rowT = (size_t)B * dout;
     const bool after = A.after != nullptr;
     const int ts = after ? T - 1 : T - 2;         // the first row that is drawn by a step; the row behind it is the carried one
     const int m0 = blockIdx.y * A.sc, mc = min(A.sc, A.S - m0);      // this workgroup's members
     const int ne = nb * dout, tot = mc * ne;      // the live elements of a member's row in this tile; of the chunk's
     const float rsq = A.rsq, qnan = __builtin_nanf("");
-    auto tri = [](int i, int p) { return i * (i + 1) / 2 + p; };
     // element e of the chunk's row: member m, element i = trial * dout + j of the tile's rows.  Its offset in (S, T, B, dout)
     // without the row's t * rowT -- in (S, B, dout) with T = 1 -- and its place in a member buffer
     auto place = [&](int e, size_t rows, size_t& go, int& lo) {
@@ -135,13 +133,8 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
     __syncthreads();
 
     // the trial of this lane and its indices
-    const int b = wave * 4 + (lane >> 4), l16 = lane & 15;
-    auto sum16 = [](float s) {
-        s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
-        return s;
-    };
-    auto isfin = [](float v) { return fabsf(v) < INFINITY; };      // (a NaN compares false)
-    // vjf_smooth_kernel's `factor`: the lower triangle at s_T becomes its Cholesky factor, a row per lane, column by column
+    const int b = ta_trial(S), l16 = ta_l16(S);
+    // ta_factor's statements (vjf_trial_algebra.h): the lower triangle at s_T becomes its Cholesky factor, a row per lane, column by column
     auto factor = [&](float* s_T) {
         bool ok = true;
         for (int j = 0; j < dout; ++j) {
@@ -151,14 +144,14 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
 #pragma unroll
             for (int e = 0; e < NO; ++e) {
                 const int i = l16 + 16 * e;
-                a[e] = (i >= j && i < dout) ? s_T[tri(i, j) * LD + b] : 0.f;
+                a[e] = (i >= j && i < dout) ? s_T[ta_tri(i, j) * LD + b] : 0.f;
             }
             for (int p = 0; p < j; ++p) {
-                const float ljp = __shfl(s_T[tri(rj, min(p, rj)) * LD + b], own, 16);
+                const float ljp = __shfl(s_T[ta_tri(rj, min(p, rj)) * LD + b], own, 16);
 #pragma unroll
                 for (int e = 0; e < NO; ++e) {
                     const int i = l16 + 16 * e;
-                    if (i >= j && i < dout) a[e] = fmaf(-s_T[tri(i, p) * LD + b], ljp, a[e]);
+                    if (i >= j && i < dout) a[e] = fmaf(-s_T[ta_tri(i, p) * LD + b], ljp, a[e]);
                 }
             }
             const float piv = __shfl(ej ? a[1] : a[0], own, 16);
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
 #pragma unroll
             for (int e = 0; e < NO; ++e) {
                 const int i = l16 + 16 * e;
-                if (i >= j && i < dout) s_T[tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
+                if (i >= j && i < dout) s_T[ta_tri(i, j) * LD + b] = i == j ? dj : a[e] / dj;
             }
         }
         return ok;
@@ -195,10 +188,10 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
             if (j < dout && b < nb) {
                 const size_t gl = (size_t)(T - 1) * rowT + row0 + (size_t)b * dout + j;
                 const float sd = expf(0.5f * A.lv[gl]);
-                nf += isfin(A.mu[gl]) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
+                nf += ta_isfin(A.mu[gl]) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
             }
         }
-        const float nfs = sum16(nf);
+        const float nfs = ta_sum16(nf);
         bad = nfs > 0.f;
         if (bad)
             for (int m = l16; m < mc; m += 16)
@@ -238,11 +231,11 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
                     const float sd = s_sd[j * LD + b], sc = sd * rsq, xj = s_x[j * LD + b];
                     float* aj = s_J + (size_t)j * dout * LD + b;
                     for (int i = 0; i < dout; ++i) aj[i * LD] = (aj[i * LD] + (i == j ? 1.f : 0.f)) * sc;
-                    nf += isfin(xj) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
+                    nf += ta_isfin(xj) && sd > 0.f && sd < INFINITY ? 0.f : 1.f;
                 }
             }
-            for (int j = dout + l16; j < d; j += 16) nf += isfin(s_x[j * LD + b]) ? 0.f : 1.f;
-            const float nfs = sum16(nf);          // (every lane of the wavefront takes part)
+            for (int j = dout + l16; j < d; j += 16) nf += ta_isfin(s_x[j * LD + b]) ? 0.f : 1.f;
+            const float nfs = ta_sum16(nf);          // (every lane of the wavefront takes part)
             bad = bad || nfs > 0.f;
         }
         __syncthreads();
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
                     const float* ap = s_J + (size_t)p * dout * LD + b;
                     float m = p == j ? 1.f : 0.f;
                     for (int i = 0; i < dout; ++i) m = fmaf(aj[i * LD], ap[i * LD], m);
-                    s_L[tri(j, p) * LD + b] = m;
+                    s_L[ta_tri(j, p) * LD + b] = m;
                 }
             }
         }
@@ -273,13 +266,13 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
                 float* yi = s_J + (size_t)i * LD + b;             // element j at yi[j * dout * LD]
                 for (int j = 0; j < dout; ++j) {
                     float s = yi[(size_t)j * dout * LD];
-                    for (int p = 0; p < j; ++p) s = fmaf(-s_L[tri(j, p) * LD + b], yi[(size_t)p * dout * LD], s);
-                    yi[(size_t)j * dout * LD] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = 0; p < j; ++p) s = fmaf(-s_L[ta_tri(j, p) * LD + b], yi[(size_t)p * dout * LD], s);
+                    yi[(size_t)j * dout * LD] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int j = dout - 1; j >= 0; --j) {
                     float s = yi[(size_t)j * dout * LD];
-                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[tri(p, j) * LD + b], yi[(size_t)p * dout * LD], s);
-                    yi[(size_t)j * dout * LD] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[ta_tri(p, j) * LD + b], yi[(size_t)p * dout * LD], s);
+                    yi[(size_t)j * dout * LD] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int j = 0; j < dout; ++j) yi[(size_t)j * dout * LD] *= s_sd[j * LD + b] * rsq;
             }
@@ -293,8 +286,8 @@ __global__ __launch_bounds__(VJF_FC_THREADS) void vjf_smooth_sample_kernel(VjfSm
                 float* zm = zc + m * MS + b;
                 for (int j = dout - 1; j >= 0; --j) {             // L^T w = z
                     float s = zm[j * LM];
-                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[tri(p, j) * LD + b], zm[p * LM], s);
-                    zm[j * LM] = s / s_L[tri(j, j) * LD + b];
+                    for (int p = j + 1; p < dout; ++p) s = fmaf(-s_L[ta_tri(p, j) * LD + b], zm[p * LM], s);
+                    zm[j * LM] = s / s_L[ta_tri(j, j) * LD + b];
                 }
                 for (int i = 0; i < dout; ++i) xm[i * LM] = xm[i * LM] - (s_x[i * LD + b] + s_g[i * LD + b]);
                 for (int j = 0; j < dout; ++j) {                  // the smoother's mean sum, then the noise term
