@@ -43,13 +43,13 @@ make_model = sc.make_model
 def decoder(name, dtype=np.float64):
     """(C (ydim, xdim), b (ydim)) of the case: the synthetic state's decoder, what make_model writes into the model."""
     a = sc._synthetic(name)
-    xdim, udim, n, ydim, B, T = CASES[name]
+    xdim, udim, n, ydim, B, T = sc.shape(name)
     return a["dec_W"].reshape(ydim, xdim).astype(dtype), a["dec_b"].reshape(ydim).astype(dtype)
 
 
 def observed(name):
     """uint8 (T, B): the fixed gap pattern -- row 0, two consecutive rows, the last row, and one trial never observed."""
-    xdim, udim, n, ydim, B, T = CASES[name]
+    xdim, udim, n, ydim, B, T = sc.shape(name)
     o = np.ones((T, B), np.uint8)
     o[0, 0::3] = 0
     o[2:4, 1::4] = 0
@@ -65,7 +65,7 @@ _IN = {}
 def inputs(name, regime="typical"):
     """float32 arrays y (T, B, ydim), u (T, B, udim) or None, x0 (B, xdim), lv0 (B, xdim) and the floats r, q: once per case and regime."""
     if (name, regime) not in _IN:
-        xdim, udim, n, ydim, B, T = CASES[name]
+        xdim, udim, n, ydim, B, T = sc.shape(name)
         r, q = REGIMES[regime]
         if name in fc.CASES:
             a = fc.inputs(name)

@@ -17,6 +17,7 @@ CASES, KINDS, Q, EPS32 = sc.CASES, sc.KINDS, sc.Q, sc.EPS32
 state, make_model, inputs, case_index = sc.state, sc.make_model, sc.inputs, sc.case_index
 MEMBERS = {"ragged3": 17, "control": 5, "wide": 5, "configB": 17, "beyond256": 5, "x24": 33, "scalar": 1}
 assert set(MEMBERS) == set(CASES)
+EXTRA_MEMBERS = {}                       # S of the shapes registered in smoother_cases.EXTRA
 # The committed factor of the rule: start at 4, at most twice the worst ratio achieved on the MI355X, never above 16.  Achieved on an
 # MI355X (profiles/sampler_margins.json has every comparison): the worst ratio is 0.390 (configB, mixed), then 0.309 (control, mixed),
 # 0.270 (x24, mixed) and 0.201 (ragged3, typical); the edge sizes (T = 1, T = 2, S = 1) are under 0.20.  F = 0.78 = 2 * 0.390.
@@ -25,8 +26,9 @@ F = 0.78
 
 def noise(name):
     """(S, T, B, xdim) fp32 standard-normal values of the case: the same for every kind."""
-    xdim, udim, n, ydim, B, T = CASES[name]
-    return np.random.default_rng(8000 + case_index(name)).standard_normal((MEMBERS[name], T, B, xdim)).astype(np.float32)
+    xdim, udim, n, ydim, B, T = sc.shape(name)
+    S = MEMBERS[name] if name in MEMBERS else EXTRA_MEMBERS[name]
+    return np.random.default_rng(8000 + case_index(name)).standard_normal((S, T, B, xdim)).astype(np.float32)
 
 
 _REF = {}

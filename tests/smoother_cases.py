@@ -26,6 +26,9 @@ CASES = dict(fc.CASES)
 CASES["x24"] = (24, 0, 40, 7, 17, 6)
 CASES["scalar"] = (1, 0, 9, 3, 16, 5)
 _INDEX = {"x24": 200, "scalar": 201}
+# Shapes other modules add for tests of their own (tests/shape_range_cases.py): name -> (shape, seed index).  They are served by every
+# helper below and by ekf_cases' and sampler_cases', and are kept out of CASES, which the family tests parametrise over.
+EXTRA = {}
 EPS32 = fc.EPS32
 Q = 0.01
 KINDS = {"typical": (math.log(1e-3), math.log(1e-1)), "tiny": (-25.0, -24.0), "mixed": (-20.0, 6.0)}
@@ -37,13 +40,20 @@ _KIND_SEED = {"typical": 0, "tiny": 300, "mixed": 600}
 F = 1.3
 
 
+def shape(name):
+    """(xdim, udim, n_rbf, ydim, B, T) of a case or of a registered shape."""
+    return CASES[name] if name in CASES else EXTRA[name][0]
+
+
 def case_index(name):
     """The case's seed offset (state 1000 +, inputs 2000 +, the sequence 6000 +)."""
+    if name in EXTRA:
+        return EXTRA[name][1]
     return _INDEX[name] if name in _INDEX else fc.case_index(name)
 
 
 def _synthetic(name):
-    xdim, udim, n, ydim, B, T = CASES[name]
+    xdim, udim, n, ydim, B, T = shape(name)
     return fc.synthetic_state(1000 + case_index(name), xdim, udim, n, ydim)
 
 
@@ -51,7 +61,7 @@ def state(name, dtype=np.float64):
     """OracleState of the case: tangent_cases.state -- for the two shapes it does not know, built the same way."""
     if name in fc.CASES:
         return tc.state(name, dtype)
-    xdim, udim, n, ydim, B, T = CASES[name]
+    xdim, udim, n, ydim, B, T = shape(name)
     a = _synthetic(name)
     s = orc.OracleState(ydim, xdim, udim, n, tuple(fc.HIDDEN), orc.GAUSSIAN)
     s.centroid, s.logwidth = a["centroid"].astype(dtype), a["logwidth"].astype(dtype)
@@ -63,7 +73,7 @@ def make_model(vjf, name, **kw):
     """A model of the case's shape with that state written into it (tangent_cases.make_model for the shapes it knows)."""
     if name in fc.CASES:
         return tc.make_model(vjf, name, **kw)
-    xdim, udim, n, ydim, B, T = CASES[name]
+    xdim, udim, n, ydim, B, T = shape(name)
     torch.manual_seed(5)
     m = vjf.VJF.make_model(ydim, xdim, udim, n, fc.HIDDEN, likelihood="gaussian", **kw)
     views = model_arrays(m)
@@ -79,7 +89,7 @@ _SEQ = {}
 def _trajectory(name):
     """(mu fp32 (T, B, xdim), u fp32 (T, B, udim) or None): once per case."""
     if name not in _SEQ:
-        xdim, udim, n, ydim, B, T = CASES[name]
+        xdim, udim, n, ydim, B, T = shape(name)
         if name in fc.CASES:
             a = fc.inputs(name)
             x0, u = a["x0"], a["u"]

@@ -11,6 +11,7 @@ import torch
 
 from tests import ekf_ref as er
 from tests import fake_backend
+from tests import tile_layouts
 from tests.fake_backend import _arr
 from oracle import vjf_oracle as orc
 from vjf_amd import _native as N
@@ -308,11 +309,7 @@ def test_the_planner_admits_the_guaranteed_shapes():
     lds = C.c_int64()
     plan = lambda n, d, dout, dy: L.vjf_ekf_plan(n, d, dout, dy, C.byref(lds))      # noqa: E731
 
-    def floats(n, d, dout, dy, vg, cl, dl):
-        doutp, dyp = (dout + 15) // 16 * 16, (dy + 15) // 16 * 16
-        ldc, ldt = (dy + 31) // 32 * 32 + 16, 16 if dout <= 16 else 48
-        return (17 * (n + d + 4 * doutp + 3 * dout + dout * dout + 3 * dout * (dout + 1) // 2 + 4 * vg * doutp + 16 + 1) + 2 * n + dout * dout
-                + (n * d + n * dout if cl else 0) + (dout * ldc + dyp * ldt if dl else 0))
+    floats = tile_layouts.ekf
     for n, d, dout, dy in ((256, 32, 24, 7), (200, 10, 10, 50), (300, 5, 5, 7), (40, 24, 24, 7), (9, 1, 1, 3), (37, 7, 5, 21), (70, 18, 17, 33)):
         assert plan(n, d, dout, dy) == 0, (n, d, dout, dy)
         assert lds.value <= 159 * 1024

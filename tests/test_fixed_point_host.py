@@ -11,6 +11,7 @@ import torch
 from tests import fake_backend
 from tests import fixed_point_cases as fpc
 from tests import fixed_point_ref as fr
+from tests import tile_layouts
 from tests.fake_backend import _arr
 from oracle import vjf_oracle as orc
 from vjf_amd import _native as N
@@ -235,9 +236,7 @@ def test_the_planner_admits_the_cases_and_the_baseline_config():
     lds = C.c_int64()
     plan = lambda n, d, dout: L.vjf_fixed_points_plan(n, d, dout, C.byref(lds))      # noqa: E731
 
-    def floats(n, d, dout, vg, cl):
-        doutp = (dout + 15) // 16 * 16
-        return 17 * (n + d + 4 * doutp + 3 * dout + dout * dout + dout * (dout + 1) // 2 + 4 * vg * doutp) + 2 * n + (n * d + n * dout if cl else 0)
+    floats = tile_layouts.fixed_points
     shapes = [(n, xdim + udim, xdim) for xdim, udim, n, ydim, B, T in fpc.CASES.values()] + [(200, 10, 10), (100, 3, 3)]
     for n, d, dout in shapes:
         assert plan(n, d, dout) == 0, (n, d, dout)

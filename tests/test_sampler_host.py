@@ -11,6 +11,7 @@ import torch
 
 from tests import fake_backend
 from tests import sampler_ref as pr
+from tests import tile_layouts
 from tests.fake_backend import _arr
 from tests.test_smoother_host import SMALL, close, cpu_only, inputs, small_model, state_of
 from oracle import vjf_oracle as orc
@@ -276,11 +277,7 @@ def plan(n, d, dout, S):
     return N.lib().vjf_smooth_sample_plan(n, d, dout, S, C.byref(sc), C.byref(lds)), sc.value, lds.value
 
 
-def floats(n, d, dout, vg, sc, cl):
-    """The layout of DESIGN.md section 3 "Posterior draws" added up."""
-    doutp = (dout + 15) // 16 * 16
-    return (17 * (n + d + 4 * doutp + 2 * dout + dout * dout + dout * (dout + 1) // 2 + 4 * vg * doutp) + 2 * n
-            + 2 * sc * 2 * ((9 * dout) | 1) + (n * d + n * dout if cl else 0))
+floats = tile_layouts.sample          # the layout of DESIGN.md section 3 "Posterior draws" added up
 
 
 def test_the_planner_admits_every_shape_the_smoother_does(monkeypatch):

@@ -11,6 +11,7 @@ import torch
 
 from tests import fake_backend
 from tests import smoother_ref as sr
+from tests import tile_layouts
 from tests.fake_backend import _arr
 from oracle import vjf_oracle as orc
 from vjf_amd import _native as N
@@ -273,9 +274,7 @@ def test_the_planner_admits_the_guaranteed_shapes():
     lds = C.c_int64()
     plan = lambda n, d, dout: L.vjf_smooth_plan(n, d, dout, C.byref(lds))      # noqa: E731
 
-    def floats(n, d, dout, vg, cl):
-        doutp = (dout + 15) // 16 * 16
-        return 17 * (n + d + 4 * doutp + 4 * dout + dout * dout + dout * (dout + 1) + 4 * vg * doutp) + 2 * n + (n * d + n * dout if cl else 0)
+    floats = tile_layouts.smooth
     for n, d, dout in ((256, 32, 24), (200, 10, 10), (300, 5, 5), (40, 24, 24), (9, 1, 1), (37, 7, 5), (70, 18, 17)):
         assert plan(n, d, dout) == 0, (n, d, dout)
         assert lds.value <= 159 * 1024

@@ -636,6 +636,10 @@ class RBFDS(Module):
         :param return_cov: also return the full covariances
         :return: SmoothResult(mean, var (T, B, xdim), cov (T, B, xdim, xdim) or None, head = (mean[0], cov of row 0)).  A trial with
             a non-finite input at some row has NaN from that row back to row 0.
+        Every xdim <= 24 with n_rbf <= 256 and udim <= 8 is accepted.  Beyond it the shape has to fit one workgroup's LDS: without a
+        control input n_rbf <= 753 at xdim = 24, 660 at 25, 463 at 27, 360 at 28, 141 at 30 and 27 at 31 (eight control inputs take 7
+        or 8 off); xdim = 32 never fits.  What does not fit raises NotImplementedError naming the limit before anything is launched.
+        These shapes are tested up to the last admitted n_rbf (tests/test_gpu_shape_range.py).
         Reads the model's state and writes none; no scratch."""
         mu, lv = (q.mean, q.logvar) if isinstance(q, Gaussian) else q
         mu, lv = dev32(mu, ndim2=False), dev32(lv, ndim2=False)
@@ -694,6 +698,8 @@ class RBFDS(Module):
             first and rows [0, k) with after = that head (and the same noise rows) second gives the bits of one call
         :return: PosteriorSamples(x (S, T, B, xdim), head = x[:, 0]).  A trial with a non-finite input at some row has NaN in every
             member from that row back to row 0.
+        Accepted wherever `smooth` is, xdim 25 to 31 beside fewer features included (its docstring has the limits; tested up to the
+        last admitted n_rbf, tests/test_gpu_shape_range.py); the members go in as many chunks per tile as the LDS asks for.
         Reads the model's state and writes none; no scratch."""
         mu, lv = (q.mean, q.logvar) if isinstance(q, Gaussian) else q
         mu, lv = dev32(mu, ndim2=False), dev32(lv, ndim2=False)
@@ -1568,6 +1574,10 @@ class VJF(Module):
             row)); `.gaussian()` is the diagonal posterior `smooth` takes (which then treats the filtered covariance as diagonal),
             `.log_likelihood()` the evidence per trial.  A trial with a non-finite observed y, u or prior at some row, or a prior
             covariance that is not positive definite, has NaN from that row on.
+        Every xdim <= 24 with n_rbf <= 256 and udim <= 8 is accepted whatever ydim is.  Beyond it the shape has to fit one
+        workgroup's LDS: without a control input n_rbf <= 461 at xdim = 24, 344 at 25 and 96 at 27 (eight control inputs take 7 or 8
+        off); xdim >= 28 never fits.  What does not fit raises NotImplementedError naming the limit before anything is launched.
+        These shapes are tested up to the last admitted n_rbf (tests/test_gpu_shape_range.py).
         Under the Poisson likelihood this raises NotImplementedError: the update is the Gaussian one (a Laplace update is not
         implemented).  Reads the model's state and writes none; no scratch."""
         if isinstance(self.likelihood, PoissonLikelihood):
