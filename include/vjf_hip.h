@@ -144,6 +144,12 @@ int vjf_state_size(const vjf_config* cfg, int64_t* n_floats);
 int vjf_state_layout(const vjf_config* cfg, int64_t* offsets, int64_t* sizes);
 /* Bytes of scratch the context needs for cfg->max_batch trials. */
 int vjf_workspace_size(const vjf_config* cfg, int64_t* bytes);
+/* The gradient-tile table of the one-launch route's training kernel for `cfg` (pure arithmetic, callable without a GPU): 16 header
+ * words -- [0] tiles, [1] segments, [2 + s] end of segment s -- then 8 words per 16x16 tile: {LDS float of the tile's first delta row,
+ * delta rows from there, LDS float of its first input row, input rows from there (the row AT that count is the ones row), first
+ * float of the tile in the late slab, the slab block's row length, slab rows stored, slab columns stored}.  `n_words` (may be null)
+ * gets the table's length; `table` (may be null) is filled when `capacity` >= that length, else -7. */
+int vjf_mega_grad_tile_table(const vjf_config* cfg, int32_t* table, int32_t capacity, int32_t* n_words);
 
 /* ---- context ------------------------------------------------------------------------------ */
 /* `state` (fp32, vjf_state_size floats) and `workspace` stay owned by the caller and must outlive

@@ -59,6 +59,7 @@ SIGNATURES = {
     "vjf_state_size": [C.POINTER(VjfConfig), C.POINTER(C.c_int64)],
     "vjf_state_layout": [C.POINTER(VjfConfig), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "vjf_workspace_size": [C.POINTER(VjfConfig), C.POINTER(C.c_int64)],
+    "vjf_mega_grad_tile_table": [C.POINTER(VjfConfig), C.POINTER(_I), _I, C.POINTER(_I)],
     "vjf_ctx_create": [C.POINTER(VjfConfig), _P, _P, C.c_int64, _P, C.POINTER(_P)],
     "vjf_ctx_destroy": [_P],
     "vjf_set_activation": [_P, C.POINTER(VjfActivation)],

@@ -92,6 +92,17 @@ int vjf_workspace_size(const vjf_config* cfg, int64_t* bytes) {
     return 0;
 }
 
+int vjf_mega_grad_tile_table(const vjf_config* cfg, int32_t* table, int32_t capacity, int32_t* n_words) {
+    VjfPlan P;
+    if (int rc = plan_for("vjf_mega_grad_tile_table", cfg, &P)) return rc;
+    const int words = vjf_mega_grad_tiles(P, nullptr);
+    if (n_words) *n_words = words;
+    if (!table) return 0;
+    if (capacity < words) return fail(-7, "vjf_mega_grad_tile_table: capacity %d < %d words", (int)capacity, words);
+    vjf_mega_grad_tiles(P, table);
+    return 0;
+}
+
 int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t workspace_bytes, void* stream,
                    vjf_ctx** out) {
     if (!cfg || !state || !workspace || !out) return fail(-1, "vjf_ctx_create: null argument");
@@ -141,16 +152,20 @@ int vjf_ctx_create(const vjf_config* cfg, float* state, void* workspace, int64_t
     if (e == hipSuccess) e = hipMemsetAsync(c->red_rls(1), 0, (size_t)P.red_len * 4, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->flag_words(), 0, 256, c->stream);
     SlabTables tb;
+    std::vector<int> gtab;
     if (c->mega_ok) {
         const VjfMegaTrialLds Lo = vjf_mega_trial_lds(P, (int)(kMegaLds / 4) - 8);
         tb = slab_tables(P, Lo, vjf_mega_slab_layout(P));
         if (e == hipSuccess) e = hipMemcpyAsync(c->mg_pidx(), tb.pidx.data(), tb.pidx.size() * 4, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(c->mg_cidx(), tb.cidx.data(), tb.cidx.size() * 4, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(c->mg_grp(), tb.grp.data(), tb.grp.size() * 4, hipMemcpyHostToDevice, c->stream);
+        gtab.resize((size_t)vjf_mega_grad_tiles(P, nullptr));
+        vjf_mega_grad_tiles(P, gtab.data());
+        if (e == hipSuccess) e = hipMemcpyAsync(c->mg_gtab(), gtab.data(), gtab.size() * 4, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(c->mg_img(), 0, (size_t)Lo.th_len * 4, c->stream);   // (its padding stays 0)
         if (e == hipSuccess) e = hipMemsetAsync(c->mega_counters(0), 0, (size_t)2 * MG_C_WORDS * 4, c->stream);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `jobs`, `tb` (host) must outlive the copies
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // `jobs`, `tb`, `gtab` (host) must outlive the copies
     if (e != hipSuccess) { delete c; return fail(-100, "vjf_ctx_create: %s", hipGetErrorString(e)); }
     allow_lds(vjf_serial_kernel, c->lds_k2);
     allow_lds(vjf_rls_post_kernel, c->lds_post);

@@ -314,7 +314,7 @@ Carve carve_ws(const VjfPlan& P, int max_batch, int njobs) {
         c.mg_gslab = take((size_t)kMegaMaxGramWg * (nbl * (nbl + 1) / 2) * 1024 * 4);
         c.mg_cnt = take((size_t)2 * MG_C_WORDS * 4);           // two counter blocks: a launch runs on one and zeroes the other for the next
         c.mg_stamps = take((32 * 32 + kMegaMaxTrialWg * 8) * 8);   // ring of role stamps | 8 words per trial workgroup (last step)
-        c.mg_pidx = take(slab_len * 4); c.mg_cidx = take(slab_len * 4); c.mg_grp = take(slab_len);
+        c.mg_pidx = take(slab_len * 4); c.mg_cidx = take(slab_len * 4); c.mg_grp = take((size_t)(VJF_GT_AT((int)slab_len) + vjf_mega_grad_tiles(P, nullptr)) * 4);   // (+ the step's gradient tiles)
         c.mg_img = take((size_t)vjf_mega_trial_lds(P, (int)(kMegaLds / 4) - 8).th_len * 4 + 64);   // the parameters in the trial role's LDS layout
         c.mg_pmsave = take((size_t)max_batch * (P.dz + 1) * 4);
         c.mg_xt = take((size_t)P.n * P.n * 4);               // row-major L^-1 (= w_chol^T) for the trial role's 16-byte operand loads
@@ -402,6 +402,7 @@ struct vjf_ctx {
     VJF_WS_REGION(float, mg_mom) VJF_WS_REGION(float, mg_xt) VJF_WS_REGION(float, mg_early) VJF_WS_REGION(float, mg_late) VJF_WS_REGION(float, mg_gslab)
     VJF_WS_REGION(float, mg_img) VJF_WS_REGION(float, mg_pmsave) VJF_WS_REGION(int, mg_pidx) VJF_WS_REGION(int, mg_cidx) VJF_WS_REGION(int, mg_grp)
 #undef VJF_WS_REGION
+    int* mg_gtab() const { return mg_grp() + VJF_GT_AT(vjf_mega_slab_layout(plan).len); }   // the gradient-tile table, behind the group words
     float* E(int gen = 0) const { return at<float>(gen ? cv.E2 : cv.E); }
     float* partial(int gen = 0) const { return at<float>(gen ? cv.partial2 : cv.partial); }
     float* red_rls(int gen) const { return at<float>(gen ? cv.red3 : cv.red2); }   // RLS statistics of even / odd steps

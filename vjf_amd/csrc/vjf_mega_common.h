@@ -110,6 +110,8 @@ struct VjfMegaArgs {
     const int* sl_pidx;                               // per slab float: the parameter it is the gradient of (index in the train region; -1: padding)
     const int* sl_cidx;                               // per slab float: that parameter's copy the trial role reads (LDS image, or the transposed aux copy; -1: none)
     const int* sl_grp;                                // per slab QUAD: 0 recognition, 1 decoder group (learning rate, freeze flag)
+                                                      // behind its slab_len / 4 words (VJF_GT_AT): the step's gradient tiles (vjf_mega_grad_tiles) -- no
+                                                      // argument of their own: a longer argument block cost vjf_mega_act_kernel scratch
     unsigned long long* stamps;                       // diagnostic (null in normal runs): s_memrealtime of workgroup 0 of each role, 32 per step
 };
 
@@ -591,9 +593,124 @@ __device__ __forceinline__ void mg_grad_tile(const float* D, int M, int m0, cons
     }
 }
 
+// ---- the gradient tiles of a step as ONE table (vjf_mega_kernel: `GTAB` in vjf_mega_trial.h).  Which tiles a step has, where their
+// operands lie in the trial role's LDS and where they go in the late slab is a function of the plan alone: the host builds the list
+// once per context (vjf_abi.hip), the kernel reads it with scalar loads.  VJF_GT_HDR header words -- [0] tiles, [1] segments, [2 + s]
+// the end (exclusive) of segment s -- then VJF_GT_ENT words per tile, in the order the per-tensor loops walk them:
+//   [0] first float of row m0 of D in LDS        [1] M - m0: rows of D from there on (lanes beyond read the zero row)
+//   [2] first float of row j0 of Bact in LDS     [3] Kin - j0: rows of Bact from there on (the lane AT it reads the ones row, beyond: zeros)
+//   [4] first float of the tile in the late slab: off + j0 ldm + m0      [5] ldm
+//   [6] rows - j0: slab rows the tile stores     [7] ldm - m0: slab columns it stores
+// A tile that would store nothing is not listed (the mean head has no bias: its column tile that holds the ones row alone).
+// The table starts on a 32-byte boundary (an entry is one s_load_dwordx8): VJF_GT_AT(slab_len) words behind the slab's group words.
+// Segment 0: decoder, both heads, the last two layers -- everything whose deltas exist when the walk starts; one more segment per
+// deeper layer (its delta is formed in between).  Wavefront w takes tiles w, w + 8, ... of the WHOLE list, segment by segment, so
+// the eight shares differ by at most one tile.
+#define VJF_GT_HDR 16
+#define VJF_GT_ENT 8
+#define VJF_GT_AT(slab_len) ((((slab_len) >> 2) + 7) & ~7)
+static inline int vjf_mega_grad_tiles(const VjfPlan& P, int* tab) {      // -> words of the table; tab == nullptr: only that
+    constexpr int LD = VJF_MG_LD;
+    const VjfMegaTrialLds Lo = vjf_mega_trial_lds(P);
+    const VjfMegaSlab SL = vjf_mega_slab_layout(P);
+    const bool compact = P.dy >= P.hmax;
+    const int d0 = compact ? Lo.py : Lo.dd, d1 = compact ? Lo.dd : Lo.dd + P.hmax * LD;
+    const int hL = P.h[P.L - 1];
+    int nt = 0, nseg = 0;
+    if (tab) for (int k = 0; k < VJF_GT_HDR; ++k) tab[k] = 0;
+    auto tensor = [&](int D, int M, int Bact, int Kin, int blk) {
+        const int ntm = (M + 15) >> 4, ntj = (Kin + 1 + 15) >> 4, ldm = SL.ldm[blk], rows = SL.rows[blk];
+        for (int tm = 0; tm < ntm; ++tm)
+            for (int tj = 0; tj < ntj; ++tj) {
+                const int m0 = 16 * tm, j0 = 16 * tj;
+                if (rows - j0 <= 0 || ldm - m0 <= 0) continue;
+                if (tab) {
+                    int* e = tab + VJF_GT_HDR + VJF_GT_ENT * nt;
+                    e[0] = D + m0 * LD; e[1] = M - m0; e[2] = Bact + j0 * LD; e[3] = Kin - j0;
+                    e[4] = SL.off[blk] + j0 * ldm + m0; e[5] = ldm; e[6] = rows - j0; e[7] = ldm - m0;
+                }
+                ++nt;
+            }
+    };
+    auto layer = [&](int l) {
+        int aoff = 0;
+        for (int q = 0; q < l - 1; ++q) aoff += P.h[q];
+        tensor(((P.L - 1 - l) & 1) ? d1 : d0, P.h[l], l > 0 ? Lo.act + aoff * LD : Lo.in, l > 0 ? P.h[l - 1] : P.din, 3 + (P.L - 1 - l));
+    };
+    auto close = [&]() { if (tab) tab[2 + nseg] = nt; ++nseg; };
+    tensor(Lo.dpy, P.dy, Lo.xt, P.dz, 0);
+    tensor(Lo.dmu, P.dz, Lo.act + (P.hsum - hL) * LD, hL, 1);
+    tensor(Lo.dlv, P.dz, Lo.act + (P.hsum - hL) * LD, hL, 2);
+    layer(P.L - 1);
+    if (P.L >= 2) layer(P.L - 2);
+    close();
+    for (int l = P.L - 3; l >= 0; --l) { layer(l); close(); }
+    if (tab) { tab[0] = nt; tab[1] = nseg; }
+    return VJF_GT_HDR + VJF_GT_ENT * nt;
+}
+
+typedef __attribute__((address_space(4))) const int mg_cst_i;       // constant address space: a uniform load from it is a scalar load
+typedef int mg_i8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) const mg_i8 mg_cst_i8;     // (a table entry: 32 bytes, 32-byte aligned)
 typedef __attribute__((address_space(3))) const float mg_lds_cf;    // an LDS pointer by type / a global-memory pointer by type: a value that
 typedef __attribute__((address_space(1))) const float mg_glb_cf;    // lives in LDS in one plan and in memory in another is read through one of
                                                                     // these on either side of a select, never through a selected generic pointer
+
+// This wavefront's tiles q, q + 8, ... < qend of the table above: mg_grad_tile's arithmetic -- the same operands, the same two chains
+// (even k-steps / odd k-steps), acc += acc1, the same store -- with the row offsets from the table and all sixteen operand reads at
+// immediate offsets from two per-lane bases.  LOOK: the NEXT tile's sixteen reads are issued in front of this tile's chains and
+// store (sixteen more live registers); they stay in front of the store because that is an asm with a memory clobber, and the
+// compiler's own wait for them comes behind it, at their use.  `q` is left at the wavefront's first tile of the next segment.
+// (LOOK fits vjf_mega_kernel's registers and is slower than none -- profiles/grad_tiles_bench.txt --: the kernel walks without it; the
+//  form stays for tools/grad_tile_bench.hip.)
+template <bool LOOK>
+__device__ __forceinline__ void mg_grad_walk(const int* table, int& q, const int qend, const float* smem, const int one, const int zero,
+                                             float* late, const bool first, const int lane) {
+    constexpr int LD = VJF_MG_LD, NW = VJF_MG_WAVES;
+    mg_cst_i* tab = (mg_cst_i*)table + VJF_GT_HDR;
+    mg_lds_cf* lds = (mg_lds_cf*)smem;
+    const int i = lane & 15, kk = lane >> 4, row = i * LD + kk;
+    // a tile's eight words by ONE scalar load, in front of everything that uses them (word by word, each at its first use, they were
+    // seven dependent round trips a tile -- and a scalar load's wait is lgkmcnt(0): it waits for every LDS read in flight as well)
+    auto ent = [&](int qq) { return *(const mg_cst_i8*)(tab + VJF_GT_ENT * qq); };
+    auto rd = [&](const mg_i8 e, float (&a)[8], float (&b)[8]) {
+        const int ao = i < e[1] ? e[0] + row : zero + kk;
+        const int bo = i < e[3] ? e[2] + row : ((i == e[3] ? one : zero) + kk);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) { a[s] = lds[ao + 4 * s]; b[s] = lds[bo + 4 * s]; }
+    };
+    auto fin = [&](const mg_i8 e, const float (&a)[8], const float (&b)[8]) {
+        vjf_f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 8; s += 2) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s + 1], b[s + 1], acc1, 0, 0, 0);
+        }
+        acc += acc1;
+        if (i < e[6] && 4 * kk < e[7]) {
+            float* p = late + e[4] + i * e[5] + 4 * kk;
+            if (!first) { acc[0] += vjf_ld_sc1(p); acc[1] += vjf_ld_sc1(p + 1); acc[2] += vjf_ld_sc1(p + 2); acc[3] += vjf_ld_sc1(p + 3); }   // (a later tile of the workgroup)
+            vjf_st4_wt(p, acc[0], acc[1], acc[2], acc[3]);
+        }
+    };
+    if (LOOK) {
+        float a0[8], b0[8], a1[8], b1[8];
+        mg_i8 e0 = {}, e1 = {};
+        if (q < qend) { e0 = ent(q); rd(e0, a0, b0); }
+        while (q < qend) {
+            if (q + NW < qend) { e1 = ent(q + NW); rd(e1, a1, b1); }
+            fin(e0, a0, b0);
+            q += NW;
+            if (q >= qend) break;
+            if (q + NW < qend) { e0 = ent(q + NW); rd(e0, a0, b0); }
+            fin(e1, a1, b1);
+            q += NW;
+        }
+    } else {
+        float a[8], b[8];
+        for (; q < qend; q += NW) { const mg_i8 e = ent(q); rd(e, a, b); fin(e, a, b); }
+    }
+}
 // loss sums of step t over the trial workgroups' late slabs: fp64, 32 strided partial sums per scalar, then a fixed xor tree -> s_sc[RS_*]
 // (the residual leaves as the mean square).  A workgroup-wide call (one barrier); read with sc1 loads behind the caller's wait.
 __device__ __forceinline__ void mg_sum_losses(const VjfMegaArgs& A, int t, float* s_sc, int tid, float Bf, int dz, bool want_resid) {

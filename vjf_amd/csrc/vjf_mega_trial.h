@@ -16,6 +16,9 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
     // kernels of the other activations have no registers for it, and vjf_mega_lite_kernel (whose moments role forms these products at
     // the sizes that matter) ran 0.3 - 1.6 us a step slower in warm-up with it (profiles/var_interior_isa.txt, var_interior_ab.txt)
     constexpr bool VSPLIT = RLS && !ACT;
+    // the gradient tiles walked from the plan's tile table (mg_grad_walk) instead of one loop per tensor: the Tanh training kernel only
+    // (profiles/grad_tiles_isa.txt); the other kernels keep grad_tensor / mg_grad_tile
+    constexpr bool GTAB = RLS && !ACT;
     const int tid0 = threadIdx.x;
     const int dz = P.dz, dy = P.dy, du = P.du, n = P.n, din = P.din, dxu = P.dxu;
     const float* S = A.state;
@@ -697,6 +700,11 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
             //      waits for them to reach memory (vmcnt counts in order).
             if (do_sgd) {
             int gbase = 0;                                                     // running tile count: gradient tiles go round the wavefronts
+            int gq = wave;                                                     // GTAB: this wavefront's next tile of the table
+            auto grad_walk = [&](int seg) {                                    // its tiles of segment `seg` (ends: header words 2 ..)
+                const int* gtab = A.sl_grp + VJF_GT_AT(A.slab_len);                // (the table lies behind the slab's group words)
+                mg_grad_walk<false>(gtab, gq, ((mg_cst_i*)gtab)[2 + seg], smem, Lo.one, Lo.zero, late, first, lane);
+            };
             auto grad_tensor = [&](const float* D, int M, const float* Bact, int Kin, int blkid) {
                 int b_off, b_ldm, b_rows;
                 mg_slab_block(P, blkid, b_off, b_ldm, b_rows);
@@ -813,17 +821,21 @@ __device__ __forceinline__ void vjf_mega_trial(const VjfPlan& P, const VjfMegaAr
                 if (P.L >= 2) { delta(P.L - 1, s_d0, s_d1); __syncthreads(); MG_PHASE(); } // da_{L-2}
                 if (first) VJF_MG_STAMP(19);
                 // gradient tiles (write-through stores into the workgroup's late slab)
-                grad_tensor(s_dpy, dy, s_xt, dz, 0);
-                grad_tensor(s_dmu, dz, hact, hL, 1);
-                grad_tensor(s_dlv, dz, hact, hL, 2);
-                layer_grads(P.L - 1, s_d0);
-                if (P.L >= 2) layer_grads(P.L - 2, s_d1);
+                if constexpr (GTAB) grad_walk(0);
+                else {
+                    grad_tensor(s_dpy, dy, s_xt, dz, 0);
+                    grad_tensor(s_dmu, dz, hact, hL, 1);
+                    grad_tensor(s_dlv, dz, hact, hL, 2);
+                    layer_grads(P.L - 1, s_d0);
+                    if (P.L >= 2) layer_grads(P.L - 2, s_d1);
+                }
                 float* cur = s_d1; float* nxt = s_d0;                          // deeper networks: the two delta buffers alternate
                 for (int l = P.L - 3; l >= 0; --l) {
                     __syncthreads(); MG_PHASE();
                     delta(l + 1, cur, nxt);
                     __syncthreads(); MG_PHASE();
-                    layer_grads(l, nxt);
+                    if constexpr (GTAB) grad_walk(P.L - 2 - l);
+                    else layer_grads(l, nxt);
                     float* tmp = cur; cur = nxt; nxt = tmp;
                 }
             }
