@@ -2,7 +2,7 @@
 """BASELINE.json configs[0]: one trial of a Lorenz system, d_z = 3, d_y = 10, Gaussian likelihood -- the counterpart of the
 reference's `script/example.py:12-47` (which fits a 2-D limit cycle the same way): make_model -> fit -> forecast.
 
-    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--score 16] [--ekf] [--plot out.png]
+    python examples/lorenz_fit.py [--epochs 20] [--T 1000] [--ensemble 64] [--lyapunov 10000] [--fixed-points 64] [--smooth] [--sample 64] [--score 16] [--ekf] [--laplace] [--plot out.png]
 
 With --ensemble S it also forecasts with uncertainty: S sampled roll-outs from the last posterior (`forecast_ensemble`), the mean and
 the +-2 sd band of the first latent at a few steps.  With --lyapunov N it prints the Lyapunov spectrum of the learned flow over N steps
@@ -16,6 +16,9 @@ draws, and the width of the band that holds 90 % of whole trajectories against t
 scores the learned dynamics (`score_forecast`): per horizon h = 1 .. K the R^2 of the h-step-ahead prediction of the latent state and of
 the observations over the record, and the skill against persistence.  With --ekf it runs the model's own extended Kalman filter over
 the record (`ekf`) and prints the evidence per row and the RMS distance between the recognition network's and the filter's means.
+With --laplace it draws spike counts from the fitted read-out (a Poisson twin of the model: the learned flow and state noise, the decoder
+scaled to rates of a few counts per row) and runs the Poisson filter over them (`laplace_filter`): the evidence per row, the largest
+gradient norm the Newton steps left, and how far the modes lie from the trajectory the counts were drawn at.
 
 Needs an MI355X (the filtering step runs as HIP kernels); `tests/test_host_cpu.py::test_lorenz_example_plumbing` runs the same
 script against the oracle-backed stand-in on the CPU."""
@@ -44,6 +47,7 @@ def main(argv=None):
     ap.add_argument("--sample", type=int, default=0, help="joint draws from the smoothed posterior (0: skip them), e.g. 64")
     ap.add_argument("--score", type=int, default=0, help="horizons of the k-step-ahead prediction error over the record (0: skip it), e.g. 16")
     ap.add_argument("--ekf", action="store_true", help="the model's own extended Kalman filter over the record: evidence and means")
+    ap.add_argument("--laplace", action="store_true", help="counts drawn from the fitted read-out and the Poisson filter over them: evidence per row")
     ap.add_argument("--plot", default=None)
     a = ap.parse_args(argv)
     import vjf_amd
@@ -128,6 +132,23 @@ def main(argv=None):
         rms = float((ek.mean.cpu()[:, 0] - m).pow(2).sum(-1).mean().sqrt())
         print(f"ekf: evidence per row = {float(ek.log_likelihood()[0]) / a.T:+.4f}   RMS |recognition - ekf mean| = {rms:.4f}"
               f"   mean variance recognition {float(logvar.detach().exp().mean()):.3e} -> ekf {float(ek.var.mean()):.3e}")
+    if a.laplace:
+        # the same for spike counts: a Poisson twin with the fitted flow, state noise and read-out (scaled so that the log rates stay
+        # within +-2), counts drawn at the filtered means, and the model's own filter over them -- the Laplace evidence row by row
+        pm = vjf_amd.VJF.make_model(ydim, xdim, udim=udim, n_rbf=a.n_rbf, hidden_sizes=[20], likelihood="poisson")
+        for dst, src in ((pm.transition.velocity.feature.centroid, model.transition.velocity.feature.centroid),
+                         (pm.transition.velocity.feature.logwidth, model.transition.velocity.feature.logwidth),
+                         (pm.transition.velocity.w_mean, model.transition.velocity.w_mean), (pm.transition.logvar, model.transition.logvar)):
+            dst.copy_(src)
+        eta = model.decoder(m.to(model.decoder.decode.weight.device))
+        gain = 2.0 / float(eta.abs().max().clamp(min=2.0))
+        pm.decoder.decode.weight.copy_(gain * model.decoder.decode.weight)
+        pm.decoder.decode.bias.copy_(gain * model.decoder.decode.bias)
+        counts = torch.poisson((gain * eta).exp().cpu(), generator=torch.Generator().manual_seed(3)).to(eta.device)
+        lf = pm.laplace_filter(counts, x0=vjf_amd.Gaussian(m[:1].to(eta.device), logvar[0].detach().to(eta.device)))
+        rms = float((lf.mean.cpu()[:, 0] - m).pow(2).sum(-1).mean().sqrt())
+        print(f"laplace_filter: mean count {float(counts.mean()):.2f}   evidence per row = {float(lf.log_likelihood()[0]) / a.T:+.4f}"
+              f"   largest grad_norm = {float(lf.grad_norm.max()):.2e}   RMS |mode - trajectory| = {rms:.4f}")
     if a.plot:
         import matplotlib
         matplotlib.use("Agg")

@@ -476,6 +476,51 @@ int vjf_ekf(const float* y, const float* u, const uint8_t* observed, const float
             const float* w_mean, const float* dec_W, const float* dec_b, const float* prior_mean, const float* prior_logvar,
             const float* prior_cov, float* mean, float* var, float* cov, float* loglik, float* cov_last, int32_t T, int32_t B,
             int32_t n, int32_t d, int32_t dout, int32_t dy, float state_var, float obs_var, void* stream);
+/* Poisson filter and model evidence: the filter of the learned generative model with count observations -- the mean map
+ * f(x, u) = x + Phi([x, u]) w_mean with J = I + A its Jacobian, a scalar state-noise variance q = state_var, the linear decoder
+ * eta = C x + b (C = dec_W (dy,dout), b = dec_b) and y_j ~ Poisson(exp(eta_j)) -- over a whole record as one call, fp32.  The
+ * posterior of each row is the Laplace approximation at the mode and the evidence is the Laplace evidence.  eta is NOT clamped
+ * (the clamp(max=10) of the training loss, vjf/likelihood.py:60, is a guard of that loss and makes the objective non-convex); the
+ * step control below keeps an overflowing rate out.  u[t] drives the transition INTO row t; row 0 is predicted from the prior
+ * with u[0].  Carried per trial: m and the lower triangle of P.  Per row t:
+ *   1. predict, exactly as vjf_ekf:  g, A at (m, u_t);  m^- = m + g;  Ls Ls^T = P;  K = (I + A) Ls;  P^- = K K^T + q I = Lp Lp^T;
+ *   2. mode, in whitened coordinates x = m^- + Lp z:
+ *        E(z):  eta = C x + b;  lam = exp(eta) (the accurate expf);  phi = sum_j (lam_j - y_j eta_j) + |z|^2 / 2;
+ *        D(z):  H = sum_j lam_j c_j c_j^T;  M = I + Lp^T H Lp = Lm Lm^T (eigenvalues >= 1);  grad = z - Lp^T C^T (y - lam);
+ *               dz = -M^-1 grad;
+ *        start: z = 0, E, D, alpha = 1;  then exactly n_iter times:  z_c = z + alpha dz;  E(z_c);  accept = phi_c <= phi, false
+ *        where phi_c is not finite;  where accepted z, phi, eta, lam become the candidate's;  D(z) runs for every trial; where
+ *        accepted dz becomes the new direction and alpha = 1, elsewhere dz stays and alpha becomes alpha / 4.  Every decision is
+ *        a per-trial select; no trip count depends on data.  The decision phi_c <= phi is taken on the difference formed term by
+ *        term, sum_j (lam_j expm1(delta_j) - y_j delta_j) + z.d + |d|^2 / 2 with d = z_c - z and delta = C Lp d: in fp32 phi_c and phi
+ *        rounded one by one agree in all their digits while z is still some 1e-3 from the mode, and their comparison is rounding;
+ *   3. posterior:  m = m^- + Lp z;  Lm Y = Lp^T;  P = Y^T Y, with the Lm of the last D;
+ *   4. loglik[t] = sum_j (y_j eta_j - lam_j - lgamma(y_j + 1)) - |z|^2 / 2 - sum log diag(Lm), the terms of the sum formed per
+ *      count before they are added up (y eta and lgamma(y + 1) cancel there, not between two large sums);
+ *   5. grad_norm[t] = |grad| of the last D: the caller sees from it whether n_iter was enough;
+ *   6. a row with observed[t,b] == 0: H = 0 and y - lam = 0 by selects (and the terms of phi), so M = I, z stays 0, P = P^-,
+ *      m = m^-, and loglik = grad_norm = 0; its y never enters arithmetic and may hold anything (NaN included);
+ *   7. poison: a trial has NaN in mean, var, cov, loglik and grad_norm from row t ON when at that row m, u or an observed y is
+ *      not finite, an observed y < 0, phi at z = 0 is not finite, a pivot of a factor (Ls, Lp, any Lm) is not positive and
+ *      finite, or loglik is not finite.  Its rows before and every other trial keep their bits.  y >= 0 need not be an integer.
+ * y (T,B,dy); u (T,B,du) or NULL (du = d - dout); observed uint8 (T,B) or NULL (every row observed); the prior of the row before
+ * row 0: prior_mean (B,dout) with EITHER prior_logvar (B,dout) OR prior_cov (B,dout,dout), its lower triangle is read -- exactly
+ * one of the two is non-NULL.  mean, var (T,B,dout); cov (T,B,dout,dout) or NULL: exactly symmetric, its diagonal is var bit for
+ * bit; loglik, grad_norm (T,B); cov_last (B,dout,dout): P of the last row, always written.  Rows [0, k) first and rows [k, T)
+ * second with prior_mean = mean[k-1], prior_cov = cov[k-1] give the bits of the undivided call.  A trial's outputs depend on that
+ * trial's inputs alone, bit for bit (not on its row, the batch, the other trials of its tile, the stream, or where the planner
+ * puts the centroids and the decoder: VJF_FC_CENTROID_LDS, VJF_LAPLACE_DECODER_LDS).  Asynchronous on `stream`, no host
+ * synchronisation, no scratch; reads the state tensors, writes none.
+ * -1 null tensor, -20 bad shape (also T < 1, dy < 1, n_iter < 1 or n_iter > 64, state_var not positive and finite, both or
+ * neither of prior_logvar / prior_cov), -21 u missing with d > dout, -11 dout > 24 or the shape is beyond one workgroup's LDS
+ * (every dout <= 16 with n <= 256 and du <= 8 fits, whatever dy is): all before the first launch and before anything is written.
+ * vjf_laplace_filter_plan: pure arithmetic, callable without a GPU: the dynamic LDS of a workgroup; -11 / -20 as the call. */
+int vjf_laplace_filter_plan(int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes);
+int vjf_laplace_filter(const float* y, const float* u, const uint8_t* observed, const float* centroid, const float* logwidth,
+                       const float* w_mean, const float* dec_W, const float* dec_b, const float* prior_mean,
+                       const float* prior_logvar, const float* prior_cov, float* mean, float* var, float* cov, float* loglik,
+                       float* grad_norm, float* cov_last, int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, int32_t dy,
+                       int32_t n_iter, float state_var, void* stream);
 /* LinearRegression.rls (vjf/module.py:79-112), in place on w_mean/w_chol/w_precision/w_pchol.
  * v: device scalar.  scratch: >= vjf_rls_scratch_size(B,n,dout) bytes.  status: device uint32
  * (0 ok, VJF_STATUS_RLS_FAILED when the state was left unchanged). */

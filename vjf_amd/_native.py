@@ -98,6 +98,8 @@ SIGNATURES = {
     "vjf_kstep_score": [_P] * 14 + [_I] * 8 + [_P],
     "vjf_ekf_plan": [_I, _I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_ekf": [_P] * 16 + [_I] * 6 + [_F, _F, _P],
+    "vjf_laplace_filter_plan": [_I, _I, _I, _I, C.POINTER(C.c_int64)],
+    "vjf_laplace_filter": [_P] * 17 + [_I] * 7 + [_F, _P],
     "vjf_rls_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],
     "vjf_blr_rls": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vjf_kalman_scratch_size": [_I, _I, _I, C.POINTER(C.c_int64)],

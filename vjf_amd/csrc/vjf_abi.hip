@@ -43,6 +43,7 @@
 #include "vjf_host_smooth_sample.h"
 #include "vjf_host_kstep.h"
 #include "vjf_host_ekf.h"
+#include "vjf_host_laplace.h"
 
 #ifdef VJF_CHAOS
 // diagnostic build: which workgroups are held, and where (vjf_handoff.h), from the environment at every entry
@@ -698,6 +699,42 @@ int vjf_ekf(const float* y, const float* u, const uint8_t* observed, const float
     a.cov = cov; a.ll = loglik; a.cov_last = cov_last; a.T = T; a.B = B; a.n = n; a.d = d; a.dout = dout; a.dy = dy; a.q = state_var;
     a.r = obs_var;
     return ekf_run(a, p, (hipStream_t)stream);
+}
+
+int vjf_laplace_filter_plan(int32_t n, int32_t d, int32_t dout, int32_t dy, int64_t* lds_bytes) {
+    if (n < 1 || dout < 1 || d < dout || dy < 1)
+        return fail(-20, "vjf_laplace_filter_plan: bad shape (n=%d d=%d dout=%d dy=%d)", n, d, dout, dy);
+    const LapPlan p = lap_plan(n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_LAPLACE_DECODER_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_laplace_filter_plan: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_LAP_MAXDOUT ? "dout <= 24 (VJF_LAP_MAXDOUT)" : "one workgroup's LDS");
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+int vjf_laplace_filter(const float* y, const float* u, const uint8_t* observed, const float* centroid, const float* logwidth,
+                       const float* w_mean, const float* dec_W, const float* dec_b, const float* prior_mean, const float* prior_logvar,
+                       const float* prior_cov, float* mean, float* var, float* cov, float* loglik, float* grad_norm, float* cov_last,
+                       int32_t T, int32_t B, int32_t n, int32_t d, int32_t dout, int32_t dy, int32_t n_iter, float state_var,
+                       void* stream) {
+    if (!y || !centroid || !logwidth || !w_mean || !dec_W || !dec_b || !prior_mean || !mean || !var || !loglik || !grad_norm || !cov_last)
+        return fail(-1, "vjf_laplace_filter: null tensor");
+    if (T < 1 || B < 1 || n < 1 || dout < 1 || d < dout || dy < 1 || n_iter < 1 || n_iter > VJF_LAP_MAXITER ||
+        !(state_var > 0.f && state_var < INFINITY) || !prior_logvar == !prior_cov)
+        return fail(-20, "vjf_laplace_filter: bad shape (T=%d B=%d n=%d d=%d dout=%d dy=%d n_iter=%d (1..64) state_var=%g%s)", T, B, n, d,
+                    dout, dy, n_iter, (double)state_var,
+                    !prior_logvar == !prior_cov ? ", exactly one of prior_logvar / prior_cov is needed" : "");
+    if (d > dout && !u) return fail(-21, "vjf_laplace_filter: u is required when d > dout");
+    const LapPlan p = lap_plan(n, d, dout, dy, fc_env_on("VJF_FC_CENTROID_LDS"), fc_env_on("VJF_LAPLACE_DECODER_LDS"));
+    if (!p.fits)
+        return fail(-11, "vjf_laplace_filter: n=%d, d=%d, dout=%d beyond %s", n, d, dout,
+                    dout > VJF_LAP_MAXDOUT ? "dout <= 24 (VJF_LAP_MAXDOUT)" : "one workgroup's LDS");
+    VjfLapArgs a{};
+    a.y = y; a.u = d > dout ? u : nullptr; a.obs = observed; a.c = centroid; a.logw = logwidth; a.w = w_mean; a.dec_W = dec_W;
+    a.dec_b = dec_b; a.prior_mean = prior_mean; a.prior_lv = prior_logvar; a.prior_cov = prior_cov; a.mean = mean; a.var = var;
+    a.cov = cov; a.ll = loglik; a.gn = grad_norm; a.cov_last = cov_last; a.T = T; a.B = B; a.n = n; a.d = d; a.dout = dout; a.dy = dy;
+    a.n_iter = n_iter; a.q = state_var;
+    return lap_run(a, p, (hipStream_t)stream);
 }
 
 int vjf_rls_scratch_size(int32_t B, int32_t n, int32_t dout, int64_t* bytes) {

@@ -17,8 +17,9 @@ namespace {
 //      The four kernels of vjf_host_smooth_sample.h did so again (.text at 0x16900); 768 bytes more put it at 0x16c00, the same
 //      offset inside a page (profiles/sampler_ab.txt).  The nine kernels of vjf_host_kstep.h: .text at 0x18800, 1024 bytes more put it
 //      at 0x18c00 (profiles/kstep_ab.txt).  The eight kernels of vjf_host_ekf.h: .text at 0x1a500, 1792 bytes more put it at 0x1ac00
-//      (profiles/ekf_ab.txt).
-__device__ __attribute__((used)) const unsigned char vjf_text_pad[4544] = {1};
+//      (profiles/ekf_ab.txt).  The eight kernels of vjf_host_laplace.h: .text at 0x1c500, 1792 bytes more put it at 0x1cc00
+//      (profiles/laplace_ab.txt).
+__device__ __attribute__((used)) const unsigned char vjf_text_pad[6336] = {1};
 
 // ---- planner.  The dout x dout block, the two triangles and one pass's partial products are in LDS beside the x step's buffers.
 //      cl: centroids and w_mean in LDS (`cen_lds`: VJF_FC_CENTROID_LDS) wherever they fit beside a pass of one group of VJF_FLOW_MV

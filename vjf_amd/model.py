@@ -77,6 +77,8 @@ LyapunovResult = namedtuple('LyapunovResult', ['exponents', 'x', 'q', 'log_stret
 FP_MAX_XDIM = 32                         # VJF_FP_MAXDOUT of vjf_fixed_points
 SM_MAX_XDIM = 32                         # VJF_SM_MAXDOUT of vjf_smooth
 EKF_MAX_XDIM = 32                        # VJF_EKF_MAXDOUT of vjf_ekf
+LAPLACE_MAX_XDIM = 24                    # VJF_LAP_MAXDOUT of vjf_laplace_filter
+LAPLACE_MAX_ITER = 64                    # VJF_LAP_MAXITER
 
 
 class FixedPointResult(namedtuple('FixedPointResult', ['x', 'residual', 'converged', 'n_iter', 'jacobian'])):
@@ -129,6 +131,24 @@ class EKFResult(namedtuple('EKFResult', ['mean', 'var', 'cov', 'loglik', 'head']
 
     def log_likelihood(self) -> Tensor:
         """The model evidence log p(y_1..T) per trial (B,), float64: the rows of `loglik` added up in float64."""
+        return self.loglik.double().sum(dim=0)
+
+
+class LaplaceFilterResult(namedtuple('LaplaceFilterResult', ['mean', 'var', 'cov', 'loglik', 'grad_norm', 'head'])):
+    """What VJF.laplace_filter returns: the modes (T, B, xdim) of the Poisson model's own filter, the marginal variances var
+    (T, B, xdim) and the full covariances cov (T, B, xdim, xdim) or None of the Laplace approximation there, the row evidences loglik
+    (T, B) ~ log p(y_t | y_1..t-1) (0 where a row is not observed), grad_norm (T, B), the norm of the whitened gradient the last Newton
+    step left (whether `n_iter` was enough), and head = (mean[-1], cov of the last row (B, xdim, xdim)): what a call on the following
+    rows takes as `before`."""
+    __slots__ = ()
+
+    def gaussian(self) -> Gaussian:
+        """The filtered marginals as `filter_sequence` returns its posterior: the diagonal Gaussian(mean, log var).  `smooth` accepts
+        it -- and then treats the filtered covariance as diagonal: the off-diagonal part of `cov` is dropped."""
+        return Gaussian(self.mean, self.var.log())
+
+    def log_likelihood(self) -> Tensor:
+        """The Laplace evidence log p(y_1..T) per trial (B,), float64: the rows of `loglik` added up in float64."""
         return self.loglik.double().sum(dim=0)
 
 
@@ -814,10 +834,11 @@ class RBFDS(Module):
         sst_y = _suffix_sst(y, K) if dy and kind != "poisson" else None
         return ForecastScore(cnt, sse_x, base_x, sse_y, base_y, _suffix_sst(mu, K), sst_y, pred, kind)
 
-    def _ekf(self, decoder, y, u, prior_mean, prior_logvar, prior_cov, state_var, obs_var, observed, return_cov):
-        """VJF.ekf behind its choice of prior and variances: the coercions, the refusals and the one call (vjf_ekf)."""
-        W, b = decoder.decode.weight, decoder.decode.bias
-        dy, dout = W.shape
+    def _record_args(self, decoder, y, u, prior_mean, prior_logvar, prior_cov, observed, what, max_xdim, variances):
+        """What `_ekf` and `_laplace_filter` share: the coercions and the refusals of a record y, its control input, the prior of the
+        row before row 0 and the `observed` flags; `variances`: (name, value) pairs that must be positive and finite.
+        :return: y (T, B, ydim), u, prior_mean, prior_logvar, prior_cov, observed (uint8 or None)"""
+        dy, dout = decoder.decode.weight.shape
         y = dev32(y, ndim2=False)
         if y.ndim == 2:
             y = y[:, None, :]                                # (T, ydim): one trial
@@ -825,9 +846,9 @@ class RBFDS(Module):
         y = y.contiguous()
         T, B = y.shape[:2]
         assert T >= 1, 'y must have at least one row'
-        if dout > EKF_MAX_XDIM:
-            raise NotImplementedError(f"ekf covers xdim <= {EKF_MAX_XDIM}, this model has xdim = {dout}")
-        for name, v in (("state_var", state_var), ("obs_var", obs_var)):
+        if dout > max_xdim:
+            raise NotImplementedError(f"{what} covers xdim <= {max_xdim}, this model has xdim = {dout}")
+        for name, v in variances:
             if not 0. < v < float('inf'):
                 raise ValueError(f"{name} must be positive and finite, got {v}")
         prior_mean = dev32(prior_mean)
@@ -847,12 +868,22 @@ class RBFDS(Module):
                 observed = observed[:, None]
             assert observed.shape == (T, B), f"observed is {tuple(observed.shape)}, expected {(T, B)}"
             observed = (observed != 0).to(device=y.device, dtype=torch.uint8).contiguous()
-        vel = self.velocity
-        n, d = vel.feature.centroid.shape
+        d = self.velocity.feature.centroid.shape[1]
         if d > dout and u is not None:
             u = dev32(u, ndim2=False)
             assert u.shape[0] == T, f"u has {u.shape[0]} rows, expected {T}"
         u = self._tangent_u(u, T, B)
+        return y, u, prior_mean, prior_logvar, prior_cov, observed
+
+    def _ekf(self, decoder, y, u, prior_mean, prior_logvar, prior_cov, state_var, obs_var, observed, return_cov):
+        """VJF.ekf behind its choice of prior and variances: the coercions, the refusals and the one call (vjf_ekf)."""
+        W, b = decoder.decode.weight, decoder.decode.bias
+        dy, dout = W.shape
+        y, u, prior_mean, prior_logvar, prior_cov, observed = self._record_args(
+            decoder, y, u, prior_mean, prior_logvar, prior_cov, observed, "ekf", EKF_MAX_XDIM, (("state_var", state_var), ("obs_var", obs_var)))
+        T, B = y.shape[:2]
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
         new = lambda *shape: torch.empty(*shape, device=y.device, dtype=torch.float32)       # noqa: E731
         mean, var, loglik, cov_last = new(T, B, dout), new(T, B, dout), new(T, B), new(B, dout, dout)
         cov = new(T, B, dout, dout) if return_cov else None
@@ -864,6 +895,30 @@ class RBFDS(Module):
             raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
         N.check(rc, "vjf_ekf")
         return EKFResult(mean, var, cov, loglik, (mean[-1], cov_last))
+
+    def _laplace_filter(self, decoder, y, u, prior_mean, prior_logvar, prior_cov, state_var, observed, n_iter, return_cov):
+        """VJF.laplace_filter behind its choice of prior and variance: the coercions, the refusals and the one call
+        (vjf_laplace_filter)."""
+        W, b = decoder.decode.weight, decoder.decode.bias
+        dy, dout = W.shape
+        if int(n_iter) != n_iter or not 1 <= n_iter <= LAPLACE_MAX_ITER:
+            raise ValueError(f"n_iter must be an integer in 1 .. {LAPLACE_MAX_ITER}, got {n_iter}")
+        y, u, prior_mean, prior_logvar, prior_cov, observed = self._record_args(
+            decoder, y, u, prior_mean, prior_logvar, prior_cov, observed, "laplace_filter", LAPLACE_MAX_XDIM, (("state_var", state_var),))
+        T, B = y.shape[:2]
+        vel = self.velocity
+        n, d = vel.feature.centroid.shape
+        new = lambda *shape: torch.empty(*shape, device=y.device, dtype=torch.float32)       # noqa: E731
+        mean, var, loglik, gnorm, cov_last = new(T, B, dout), new(T, B, dout), new(T, B), new(T, B), new(B, dout, dout)
+        cov = new(T, B, dout, dout) if return_cov else None
+        rc = N.lib().vjf_laplace_filter(N.ptr(y), N.ptr(u), N.ptr(observed), N.ptr(vel.feature.centroid), N.ptr(vel.feature.logwidth),
+                                        N.ptr(vel.w_mean), N.ptr(W), N.ptr(b), N.ptr(prior_mean), N.ptr(prior_logvar),
+                                        N.ptr(prior_cov), N.ptr(mean), N.ptr(var), N.ptr(cov), N.ptr(loglik), N.ptr(gnorm),
+                                        N.ptr(cov_last), T, B, n, d, dout, dy, int(n_iter), state_var, stream_ptr())
+        if rc == -11:                             # the shape is beyond the plan (vjf_laplace_filter_plan): nothing was launched
+            raise NotImplementedError(N.lib().vjf_last_error().decode("utf-8", "replace"))
+        N.check(rc, "vjf_laplace_filter")
+        return LaplaceFilterResult(mean, var, cov, loglik, gnorm, (mean[-1], cov_last))
 
     @torch.no_grad()
     def update(self, xt: Tensor, xs: Tensor, ut: Tensor = None, *, warm_up=False):
@@ -1578,11 +1633,11 @@ class VJF(Module):
         workgroup's LDS: without a control input n_rbf <= 461 at xdim = 24, 344 at 25 and 96 at 27 (eight control inputs take 7 or 8
         off); xdim >= 28 never fits.  What does not fit raises NotImplementedError naming the limit before anything is launched.
         These shapes are tested up to the last admitted n_rbf (tests/test_gpu_shape_range.py).
-        Under the Poisson likelihood this raises NotImplementedError: the update is the Gaussian one (a Laplace update is not
-        implemented).  Reads the model's state and writes none; no scratch."""
+        Under the Poisson likelihood this raises NotImplementedError: the update is the Gaussian one; `laplace_filter` is the
+        filter of a Poisson model.  Reads the model's state and writes none; no scratch."""
         if isinstance(self.likelihood, PoissonLikelihood):
             raise NotImplementedError("ekf needs the Gaussian likelihood: under the Poisson likelihood the update is not Gaussian "
-                                      "(a Laplace update is not implemented)")
+                                      "(use laplace_filter)")
         if x0 is not None and before is not None:
             raise ValueError("give x0 (a diagonal Gaussian) or before (mean, cov), not both")
         y = dev32(y, ndim2=False)
@@ -1598,6 +1653,50 @@ class VJF(Module):
         state_var = float(self.transition.logvar.exp()) if state_var is None else float(state_var)
         obs_var = float(self.likelihood.logvar.exp()) if obs_var is None else float(obs_var)
         return self.transition._ekf(self.decoder, y, u, p_mean, p_lv, p_cov, state_var, obs_var, observed, return_cov)
+
+    def laplace_filter(self, y: Tensor, u: Tensor = None, *, x0: Gaussian = None, before: Tuple[Tensor, Tensor] = None,
+                       state_var: float = None, observed: Tensor = None, n_iter: int = 8,
+                       return_cov: bool = False) -> LaplaceFilterResult:
+        """The filter of the learned generative model with count observations over a record as ONE C-ABI call (vjf_laplace_filter;
+        the contract is stated in include/vjf_hip.h): the mean map and its Jacobian, the state noise, the linear decoder
+        eta = C x + b and y ~ Poisson(exp(eta)) -- no recognition network, and no clamp on eta.  Per row the posterior is the Laplace
+        approximation at the mode, found by `n_iter` Newton steps with a per-trial step control, and loglik is the Laplace evidence
+        of the row; rows that were not observed are stepped over.  `ekf` is the same for a Gaussian model.
+        :param y: (T, B, ydim) of counts (y >= 0; integers are not required); (T, ydim) is one trial
+        :param u: (T, B, udim): u[t] drives the transition INTO row t, as in `filter`; row 0 is predicted from the prior with u[0]
+        :param x0: the prior of the row before row 0: None (the model's `prior`) or a Gaussian of (B, xdim)
+        :param before: (mean (B, xdim), cov (B, xdim, xdim)) in x0's place, such as a previous result's `head`: rows [0, k) first and
+            rows [k, T) with before = that head second give the bits of one call.  Giving both x0 and before is a ValueError
+        :param state_var: the scalar state-noise variance, default exp(transition.logvar).  Reading the default copies one scalar to
+            the host, which synchronises the stream; pass a float to stay asynchronous
+        :param observed: (T, B) of booleans or 0 / 1, None: every row.  A row that is not observed is predicted only (its loglik and
+            grad_norm are 0) and its y is never used: it may hold NaN
+        :param n_iter: Newton steps per row, 1 .. 64; `grad_norm` of the result tells whether they were enough
+        :param return_cov: also return the full covariances of every row
+        :return: LaplaceFilterResult(mean, var (T, B, xdim), cov (T, B, xdim, xdim) or None, loglik, grad_norm (T, B),
+            head = (mean[-1], cov of the last row)); `.gaussian()` is the diagonal posterior `smooth` takes, `.log_likelihood()` the
+            evidence per trial.  A trial with a non-finite or negative observed y, a non-finite u or prior at some row, a prior
+            covariance that is not positive definite or rates that overflow at the prediction has NaN from that row on.
+        Every xdim <= 16 with n_rbf <= 256 and udim <= 8 is accepted whatever ydim is; xdim <= 24 is accepted where the shape fits
+        one workgroup's LDS, and xdim > 24 never.  What does not fit raises NotImplementedError naming the limit before anything is
+        launched.  Under the Gaussian likelihood this raises NotImplementedError: `ekf` is that model's filter.
+        Reads the model's state and writes none; no scratch."""
+        if not isinstance(self.likelihood, PoissonLikelihood):
+            raise NotImplementedError("laplace_filter needs the Poisson likelihood: ekf is the filter of a Gaussian model")
+        if x0 is not None and before is not None:
+            raise ValueError("give x0 (a diagonal Gaussian) or before (mean, cov), not both")
+        y = dev32(y, ndim2=False)
+        B = 1 if y.ndim == 2 else y.shape[1]
+        p_mean = p_lv = p_cov = None
+        if before is not None:
+            p_mean, p_cov = before
+        elif x0 is not None:
+            p_mean, p_lv = x0.mean, x0.logvar
+        else:
+            one = torch.ones(B, self.xdim, device=self._blob.device)
+            p_mean, p_lv = one * torch.atleast_2d(self.mean), one * torch.atleast_2d(self.logvar)
+        state_var = float(self.transition.logvar.exp()) if state_var is None else float(state_var)
+        return self.transition._laplace_filter(self.decoder, y, u, p_mean, p_lv, p_cov, state_var, observed, n_iter, return_cov)
 
     def sample_posterior(self, q: Union[Gaussian, Tuple[Tensor, Tensor]], u: Tensor = None, n_sample: int = 16, *,
                          state_var: float = None, noise: Tensor = None, after: Tensor = None) -> PosteriorSamples:
